@@ -1,7 +1,12 @@
 """Benchmark: batched time-domain tube synthesis on MI355X.
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seconds S] [--fs HZ]
-                [--workload static|fricatives|vcv]
+                [--workload static|fricatives|vcv] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line: the metric, the
+step's times and the objects computed from the timed steps alone (roofline, fp64).  --full adds
+what takes runs of its own: the CPU baseline and the error against the reference build, the
+"configs" sub-objects and, at N > 1, the check of the gathered audio (everything from "the CPU
+baseline" on below).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 For N > 1 either run `python bench.py --gpus N` (it starts the N ranks itself: a child
 torch.distributed.run, one rank per GPU) or launch it under torch.distributed.run with --gpus
 equal to WORLD_SIZE (anything else is refused).
@@ -17,10 +22,10 @@ the RCCL id, barriers and the max-over-ranks time.
 Printed (rank 0): one JSON line with the BASELINE metric (whole-node samples/s), the roofline
 object of the dominant kernel (HBM, as the north star asks, with the kernel's own launch times
 from HIP events around every launch: afs_kernel_times), the fp64 object (the path's binding
-resource: algorithmic flops counted from the restatement, profiles/flops_per_sample.json) and
-the CPU baseline (the reference's own sources, oracle/_ref, timed on this host's cores over a
-bounded sample, plus the single-core config-1 figure).  On one GPU the line also carries
-"configs": config 2 (1024 static vowels: one utterance per SIMD, the voice kernel's per-sample
+resource: algorithmic flops counted from the restatement, profiles/flops_per_sample.json) and,
+with --full, the CPU baseline (the reference's own sources, oracle/_ref, timed on this host's
+cores over a bounded sample, plus the single-core config-1 figure).  On one GPU the --full line
+also carries "configs": config 2 (1024 static vowels: one utterance per SIMD, the voice kernel's per-sample
 latency), config 5 (8192 fricatives, velum 1.0 cm^2) and config 3 (8192 VCV utterances through
 playTargetSequence), each timed over a few steps with its own launch times, roofline, fp64
 object, reference CPU rate and error against the reference build, and "config4_shard": config 4's
@@ -216,6 +221,7 @@ def measure(args, ctx, dev, stream, workload: str, B: int, first: int, world: in
     else:
         transport = _NoGather()
     pcm = sharding.PcmGather(lambda x, o: ctx.to_int16(x, out=o), (B, m.T), world, rank, transport, device=dev)
+    m.pcm = pcm
 
     for _ in range(warmup):
         synth()
@@ -262,9 +268,9 @@ def measure(args, ctx, dev, stream, workload: str, B: int, first: int, world: in
                    "transport": "rccl (afs_gather_pcm)" if comm is not None else "gloo via the host (test transport)",
                    "gather_timing": "HIP events on the comm's stream around each afs_gather_pcm "
                                     "(afs_comm_gather_times); the gather overlaps the next step's synthesis"}
-        # self-check of the exchange: rank 0 compares the int16 rows it received (the last step's
-        # slot) with the same utterances synthesized on rank 0 alone
-        if rank == 0:
+        # --full: self-check of the exchange: rank 0 compares the int16 rows it received (the last
+        # step's slot) with the same utterances synthesized on rank 0 alone
+        if rank == 0 and args.full:
             edges = sharding.edge_utterances(world, B)
             root = pcm.result((pcm.k - 1) % len(pcm.bufs))
             rows = torch.stack([root[r, j] for r, j, _ in edges]).cpu()
@@ -395,6 +401,31 @@ def cpu_leg(args, m: Measured, n: int):
     return cpu_baseline(jobs, args.fs, n, gpu_out, what, config1_frames(args.fs))
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of the two arrays together
+
+
+def dump_outputs(path: str, m: Measured) -> None:
+    """--dump-outputs (rank 0): what the timed path handed back in its last step, as it lies in HBM
+    after the timed steps -- path/audio.npy, the synthesis call's float64 audio [rows, T] of this
+    rank's shard, and path/pcm.npy, the int16 conversion of it (N > 1: as gathered from every rank,
+    [world x B, T] in utterance order) stored as float32, which holds every int16 exactly.  An output
+    above DUMP_BYTES is sampled: rows drawn without replacement by a generator seeded with 0 and
+    sorted (and, for very long utterances, the first samples of each), so the same arguments give the
+    same rows; the frames and seeds are functions of the arguments alone (workloads.py)."""
+    import torch
+
+    pcm = m.pcm.result((m.pcm.k - 1) % len(m.pcm.bufs))
+    pcm = pcm.reshape(-1, pcm.shape[-1])
+    cols = min(m.T, DUMP_BYTES // 12)
+    n = max(1, DUMP_BYTES // (12 * cols))  # 8 B of audio + 4 B of pcm per sample
+    os.makedirs(path, exist_ok=True)
+    for name, t, dtype in (("audio", m.out_dev, torch.float64), ("pcm", pcm, torch.float32)):
+        total = t.shape[0]
+        rows = np.arange(total) if total <= n else np.sort(np.random.default_rng(0).choice(total, n, replace=False))
+        part = t[torch.from_numpy(rows).to(t.device)][:, :cols].to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), part)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -402,6 +433,13 @@ def main() -> None:
                          "--gpus N > 1 starts the N ranks itself (torch.distributed.run as a child process)")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline and the error against the reference "
+                         "build, the config-2 / 5 / 3 and config-4-shard sub-objects (one GPU), the check of the "
+                         "gathered audio (N > 1); --no-cpu-baseline and --no-sub-configs narrow it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/audio.npy (float64) and "
+                         "DIR/pcm.npy (the int16 audio as float32): a fixed sample of rows when the batch is large")
     ap.add_argument("--global-batch", type=int, default=65536,
                     help="the metric's batch (BASELINE config 4: 65536 utterances), split over the GPUs (strong "
                          "scaling: 65536 on one GPU, 8192 per GPU at 8)")
@@ -416,13 +454,13 @@ def main() -> None:
     ap.add_argument("--cpu-utterances", type=int, default=128,
                     help="CPU baseline: utterances of the headline's bounded sample (128 x 1 s: ~38 core-seconds of "
                          "the reference's work, ~2.5 s on the box's 16-CPU share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--workload", choices=("static", "fricatives", "vcv"), default="static",
                     help="static: config-4 shard of static vowels (default); fricatives: config 5 "
                          "(fricatives + velum 1.0 cm^2); vcv: config-3 VCV utterances through "
                          "playTargetSequence (per-sample tubes, hop 1)")
     ap.add_argument("--no-sub-configs", action="store_true",
-                    help="skip the config-5 / config-3 sub-objects (one GPU, default workload only)")
+                    help="--full without the config-5 / config-3 sub-objects (one GPU, default workload only)")
     ap.add_argument("--lanes", type=int, choices=(16, 64), default=None,
                     help="tree solver: force 16 (throughput kernel) or 64 (voice kernel) lanes per utterance; "
                          "default: the library's choice for the batch")
@@ -507,9 +545,15 @@ def main() -> None:
         comm = Comm(ctx, uid[0], rank, world)
 
     m = measure(args, ctx, dev, stream, args.workload, B, first, world, rank, comm, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m)
+    m.pcm = None  # (the int16 buffers go back to the allocator before anything else runs)
+    # --full only: the CPU legs and the sub-objects, which take runs of their own
+    cpu_legs = args.full and not args.no_cpu_baseline
+    sub_configs = args.full and not args.no_sub_configs
     # one GPU: config 5 and config 3 are timed too (sub-objects, a few steps each)
     subs = []
-    if world == 1 and args.workload == "static" and not args.no_sub_configs:
+    if world == 1 and args.workload == "static" and sub_configs:
         # config 2 (1024 static vowels: one utterance per SIMD, the voice kernel's per-sample latency)
         subs.append(("config2", measure(args, ctx, dev, stream, "static", args.config2_batch, 0, world, rank, None,
                                         args.sub_steps, 1)))
@@ -518,7 +562,7 @@ def main() -> None:
                                         args.sub_steps, 1)))
     # one GPU: config 4's per-GPU shard at 8 GPUs (8192 utterances), the headline of rounds 1-4
     shard = None
-    if world == 1 and args.workload == "static" and not args.no_sub_configs and args.sub_batch != B:
+    if world == 1 and args.workload == "static" and sub_configs and args.sub_batch != B:
         shard = measure(args, ctx, dev, stream, "static", args.sub_batch, 0, 1, 0, None, args.sub_steps, 1)
         n = min(B, args.sub_batch)
         # batch independence: the shard's utterances are the batch's first ones, bit for bit
@@ -565,14 +609,15 @@ def main() -> None:
         }
         if world > 1:
             result["multi_gpu"] = m.multi
+        if world > 1 and args.full:
             result["gather_check"] = m.gather_check
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and cpu_legs:
             # (no CPU timing at N > 1: the error of rank 0's first utterances against the reference build)
             _, max_abs, max_rms = cpu_leg(args, m, min(8, B))
             result["max_abs_err_vs_cpu_ref"] = max_abs
             result["max_rms_err_vs_cpu_ref"] = max_rms
             result["cpu_ref_utterances"] = min(8, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_legs:
             cb, max_abs, max_rms = cpu_leg(args, m, min(args.cpu_utterances, B))
             result["cpu_baseline"] = cb
             result["max_abs_err_vs_cpu_ref"] = max_abs
@@ -598,7 +643,7 @@ def main() -> None:
                     # the voice kernel's per-sample latency: one utterance per wave, one wave per SIMD
                     o["us_per_sample_per_utterance"] = ds["roofline"]["avg_launch_ms"] * 1e3 / (
                         ms.T / max(1.0, ds["roofline"]["launches_per_step"]))
-                if not args.no_cpu_baseline:
+                if cpu_legs:
                     cb, max_abs, max_rms = cpu_leg(args, ms, min(args.sub_cpu_utterances, ms.B))
                     o["cpu_reference_per_core_samples_per_s"] = cb["per_core_samples_per_s"]
                     o["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample",

@@ -118,7 +118,7 @@ def test_bench_world2_gather_check_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"),
            "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "24", "--seconds", "0.05",
-           "--no-cpu-baseline", "--gather-transport", "gloo", "--one-device"]
+           "--full", "--no-cpu-baseline", "--gather-transport", "gloo", "--one-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=root)

@@ -6,7 +6,7 @@
 # usage: tools/session.sh TAG [steps...]      outputs under gpurun_out/TAG/
 # steps (default: test smoke bench prof):
 #   test    pytest -m gpu (PK="-k expression" narrows it)      smoke  __graft_entry__.smoke()
-#   bench   bench.py $BENCH_ARGS                                prof   rocprofv3 --kernel-trace --stats of bench.py
+#   bench   bench.py --full $BENCH_ARGS                         prof   rocprofv3 --kernel-trace --stats of bench.py
 #   pmc     FETCH_SIZE and WRITE_SIZE passes (one rocprofv3 run each) of one bench step
 #   sq      SQ fp64 pass (tools/pmc_sq_fp64.py summarises it)  mix    three SQ instruction-mix passes
 #   calib   the FETCH_SIZE calibration probe                    pp     per-phase cycle profile (tools/phase_prof)
@@ -36,7 +36,7 @@ for s in $STEPS; do
     test)  timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PK:+-k "$PK"} > $OUT/pytest_gpu.log 2>&1; ok $? pytest
            grep -A14 "parity report" $OUT/pytest_gpu.log | cut -c1-240; tail -4 $OUT/pytest_gpu.log ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; ok $? smoke ;;
-    bench) timeout -k 10 600 python bench.py $BA > $OUT/bench.json 2> $OUT/bench.err; ok $? bench; cat $OUT/bench.json ;;
+    bench) timeout -k 10 600 python bench.py --full $BA > $OUT/bench.json 2> $OUT/bench.err; ok $? bench; cat $OUT/bench.json ;;
     prof)  (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o run -- python3 $R/bench.py $BA --no-cpu-baseline --no-sub-configs) > $OUT/prof.log 2>&1; ok $? prof ;;
     pmc)   pmc pmc_fetch FETCH_SIZE; pmc pmc_write WRITE_SIZE ;;
     sq)    pmc pmc_sq "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_FLOPS_FP64 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU" ;;
