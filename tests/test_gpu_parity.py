@@ -179,13 +179,15 @@ def test_launch_split_is_bitwise(oracle, solver, monkeypatch):
     """The tree path's launches (one per second of audio by default; AFS_LAUNCH_SAMPLES lowers it)
     carry the lane and LDS state, the hop records and the frame cache across their boundaries: a
     call split into launches of 1000 samples -- boundaries inside hops of 441 -- gives the same
-    audio bit for bit, static vowels and fricatives with their noise sources."""
+    audio bit for bit, static vowels and fricatives with their noise sources.  So do launches of 999
+    samples (odd: the wave pairs' displacement double buffer ends each launch in its second half)
+    and of 17 (odd, below the hop records' minimum hop and one more than an output line)."""
     from areafunctionsynthesis_amd.synthesizer import Context
     frames = np.stack([static_frames(oracle, v, 12, velum=vel)
                        for v, vel in (("a:", 0.0), ("s", 1.0), ("i:", 0.0), ("S", 0.0), ("u:", 0.5))])
     seeds = np.arange(7, 7 + len(frames), dtype=np.uint32)
     ys = []
-    for env in (None, "1000"):
+    for env in (None, "1000", "999", "17"):
         if env is None:
             monkeypatch.delenv("AFS_LAUNCH_SAMPLES", raising=False)
         else:
@@ -196,9 +198,11 @@ def test_launch_split_is_bitwise(oracle, solver, monkeypatch):
             kt = ctx.kernel_times()
         finally:
             ctx.close()
-        assert kt["synth_launches"] == (1 if env is None else -(-11 * 441 // 1000))
+        assert kt["synth_launches"] == (1 if env is None else -(-11 * 441 // int(env)))
     assert np.array_equal(ys[0], ys[1])
     assert np.isfinite(ys[0]).all()
+    for y, env in zip(ys[2:], ("999", "17")):
+        assert np.array_equal(ys[0], y), (env, float(np.abs(ys[0] - y).max()))
 
 
 def test_plan_budget_chunked_hop_mode(oracle, monkeypatch):

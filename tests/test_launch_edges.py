@@ -1,0 +1,341 @@
+"""Launch and session boundaries of the synthesis kernels: what joins one launch to the next.
+
+test_gpu_parity.py checks single launches of even, line-sized lengths into host buffers; a
+real-time caller runs a session whose call length changes from buffer to buffer and may hand the
+library device memory at any alignment.  Checked here:
+  * sessions with a call length that changes on every call (oracle_lib.CALL_SCHEDULE: odd launches,
+    launches below one 16-sample output line, the dense and the hop-record kernels alternating on
+    one saved state, num_samples = 0) against the oracle's own incremental calls (pinned to the
+    reference in test_oracle.py), the rand() call counts, and reset;
+  * the wave pairs' glottis displacement double buffer (X_RELX / X_RELX2, picked by the parity of
+    the launch-local sample index and copied back after an odd launch, tree_kernel.h tree_pair_run)
+    bit for bit against the one-wave kernel, which has no second buffer;
+  * K1's 128-byte output window and the section-25 pressure rows laid out congruent to it
+    (afs_capi.cpp run_chunks) with device output at every kind of alignment: the same audio as
+    into a host buffer, and the memory on both sides of the rows untouched.
+Bounds: GOLD_TOL against the oracle (every sequence stays under the 2048 samples it is defined
+for); bit for bit wherever two GPU paths are designed to be identical.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from areafunctionsynthesis_amd.frames import FRAME_DTYPE
+from oracle_lib import CALL_SCHEDULE, SCHEDULE_SHAPES, schedule_frames
+
+pytestmark = pytest.mark.gpu
+
+GOLD_TOL = 1e-9
+FS = 44100.0
+TREE_SOLVERS = ("tree16", "tree64")
+SOLVERS = ("cholesky",) + TREE_SOLVERS
+LANES = {"tree16": 16, "tree64": 64}
+
+FRICATIVES = ("s", "f", "S", "x", "C", "z")
+# (shapes, first shape, velum openings): vowels and plosives, fricatives with the velum open
+# (noise sources and rand() live), plain vowels
+VOICES = ((SCHEDULE_SHAPES, 0, (0.0, 0.6)), (FRICATIVES, 0, (0.6, 1.0)), (SCHEDULE_SHAPES, 3, (0.0, 0.6)),
+          (FRICATIVES[::-1], 2, (1.0, 0.6)), (("a:", "e:", "i:", "o:", "u:"), 1, (0.0, 0.0)),
+          (SCHEDULE_SHAPES, 1, (0.3, 0.0)), (FRICATIVES, 3, (1.0, 1.0)), (SCHEDULE_SHAPES, 4, (0.0, 0.0)),
+          (FRICATIVES[::-1], 5, (0.6, 0.6)), (SCHEDULE_SHAPES, 5, (0.6, 0.0)))
+
+
+@pytest.fixture(scope="module")
+def contexts():
+    from areafunctionsynthesis_amd.synthesizer import Context
+    cache = {}
+
+    def get(solver, **opt):
+        key = (solver, tuple(sorted(opt.items())))
+        if key not in cache:
+            if solver in LANES:
+                cache[key] = Context(FS, solver="tree", lanes=LANES[solver], **opt)
+            else:
+                cache[key] = Context(FS, solver=solver, **opt)
+        return cache[key]
+
+    yield get
+    for c in cache.values():
+        c.close()
+
+
+_FRAMES = {}
+
+
+def voice_frames(oracle, B, two_mass=False):
+    """frames[B, 1 + len(CALL_SCHEDULE)]: voice u plays VOICES[u % len(VOICES)], a frame sequence of
+    its own that changes on every call (computed once, shared and left unchanged)."""
+    key = bool(two_mass)
+    if key not in _FRAMES:
+        _FRAMES[key] = np.stack([schedule_frames(oracle, shapes, start, velum, two_mass=two_mass)
+                                 for shapes, start, velum in VOICES])
+        _FRAMES[key].setflags(write=False)
+    return np.ascontiguousarray(_FRAMES[key][np.arange(B) % len(VOICES)])
+
+
+_ORACLE = {}
+
+
+def oracle_session(oracle, frames, seeds, opt):
+    """The oracle's incremental calls over CALL_SCHEDULE for every voice: (the chunks of every call
+    [call][voice], rand() calls per voice); computed once per option set."""
+    key = (frames.shape[0], tuple(int(s) for s in seeds), tuple(sorted(opt.items())))
+    if key not in _ORACLE:
+        chunks = [[] for _ in CALL_SCHEDULE]
+        draws = []
+        for u in range(frames.shape[0]):
+            h = oracle.create(FS, int(seeds[u]), opt)
+            try:
+                assert oracle.call(h, frames[u, 0], 441).size == 0  # the latch
+                for k, n in enumerate(CALL_SCHEDULE):
+                    chunks[k].append(oracle.call(h, frames[u, k + 1], n))
+                draws.append(oracle.rng_calls(h))
+            finally:
+                oracle.destroy(h)
+        _ORACLE[key] = ([np.stack(c) for c in chunks], np.array(draws, dtype=np.int64))
+    return _ORACLE[key]
+
+
+def run_session(ctx, frames, seeds, rows=None):
+    """A session over CALL_SCHEDULE -> (the audio of every call, first `rows` voices; rand() calls
+    or None for the lane solver; the session, still open)."""
+    from areafunctionsynthesis_amd.synthesizer import Synthesizer
+    B = frames.shape[0]
+    syn = Synthesizer(ctx, B, seeds)
+    assert syn.synthesize_signal_tds(frames[:, 0], 441).shape == (B, 0)  # latch only
+    parts = [syn.synthesize_signal_tds(frames[:, k + 1], n)[:rows].copy() for k, n in enumerate(CALL_SCHEDULE)]
+    return parts, syn
+
+
+@pytest.mark.parametrize("opt", [{}, {"radiation_from_skin": 0}, {"glottis_model": 1}],
+                         ids=["default", "no_skin_radiation", "two_mass"])
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_session_varying_call_lengths_vs_oracle(contexts, oracle, parity_report, solver, opt):
+    """A session of 5 voices (odd, not a multiple of 4: rows of odd length are misaligned and the
+    16-lane block has stand-in slots) called with CALL_SCHEDULE's lengths, every voice with frames of
+    its own that change on every call, against the oracle's calls with the same lengths; the rand()
+    call counts at the end; the same audio bit for bit after a reset.  Without skin radiation K6
+    runs the output filter alone instead of the tone filter's loop."""
+    B = 5
+    frames = voice_frames(oracle, B, two_mass=opt.get("glottis_model") == 1)
+    seeds = np.arange(21, 21 + B, dtype=np.uint32)
+    want, want_draws = oracle_session(oracle, frames, seeds, opt)
+    assert want_draws[1] > 0 and want_draws[3] > 0  # (the fricative voices draw noise)
+    ctx = contexts(solver, **opt)
+    parts, syn = run_session(ctx, frames, seeds)
+    try:
+        worst = (-1.0, None)
+        for k, n in enumerate(CALL_SCHEDULE):
+            assert parts[k].shape == (B, max(n, 1)), (k, n)
+            assert np.isfinite(parts[k]).all(), (k, n)
+            err = np.abs(parts[k] - want[k]).max(axis=1)
+            print(f"call {k + 1} n={n}: max |gpu - oracle| per voice {err}")
+            if float(err.max()) > worst[0]:
+                worst = (float(err.max()), (k + 1, n, int(err.argmax())))
+        parity_report.append(f"session with varying call lengths [{solver}, {opt or 'default'}]: {B} voices x 844 "
+                             f"samples vs the oracle's calls: max |err| {worst[0]:.2e} at (call, n, voice) {worst[1]}")
+        assert worst[0] <= GOLD_TOL, worst
+        if solver in TREE_SOLVERS:
+            assert np.array_equal(syn.rng_draws(), want_draws)
+        syn.reset(seeds)
+        assert syn.synthesize_signal_tds(frames[:, 0], 441).shape == (B, 0)
+        for k, n in enumerate(CALL_SCHEDULE):
+            assert np.array_equal(syn.synthesize_signal_tds(frames[:, k + 1], n), parts[k]), (k, n)
+    finally:
+        syn.close()
+
+
+@pytest.mark.parametrize("glottis_model", [0, 1], ids=["triangular", "two_mass"])
+def test_voice_pair_sessions_equal_one_wave_bitwise(contexts, oracle, glottis_model):
+    """The 64-lane wave pairs (sessions of up to 1024 voices) against the one-wave kernel (1025
+    voices), which computes the same values without the pairs' second displacement buffer: the same
+    8 voices in both sessions over CALL_SCHEDULE -- mostly odd launches, after each of which the pair
+    copies X_RELX2 back into X_RELX -- give the same audio and rand() call counts bit for bit."""
+    ctx = contexts("tree64", glottis_model=glottis_model)
+    assert ctx.synthesis_kernel(1025) == "tree_synth_kernel"
+    assert ctx.synthesis_kernel(8) == "tree_pair64_kernel"
+    B, rows = 1025, 8
+    frames = voice_frames(oracle, B, two_mass=glottis_model == 1)
+    seeds = np.arange(1, B + 1, dtype=np.uint32)
+    one, syn1 = run_session(ctx, frames, seeds, rows)
+    try:
+        draws1 = syn1.rng_draws()[:rows]
+    finally:
+        syn1.close()
+    pair, syn2 = run_session(ctx, np.ascontiguousarray(frames[:rows]), seeds[:rows])
+    try:
+        draws2 = syn2.rng_draws()
+    finally:
+        syn2.close()
+    for k, n in enumerate(CALL_SCHEDULE):
+        assert one[k].shape == pair[k].shape == (rows, max(n, 1))
+        assert np.isfinite(one[k]).all()
+        diff = np.abs(one[k] - pair[k]).max()
+        print(f"call {k + 1} n={n}: max |one wave - pair| {diff:.3e}")
+        assert np.array_equal(one[k], pair[k]), (k + 1, n, float(diff))
+    assert draws1[1] > 0 and np.array_equal(draws1, draws2)
+
+
+# --- device output at arbitrary alignment ------------------------------------------------------
+
+SENTINEL = -7.25e77  # (no audio sample comes near it)
+PAD = 64             # sentinel doubles on each side of the rows at least
+OFFSETS = (0, 1, 9, 15)  # doubles from a 128-byte line to the first row
+
+
+def device_out(B, T, off):
+    """(buffer, out): a device buffer of sentinels whose base is line-aligned and a contiguous
+    [B, T] view of it starting PAD + off doubles in."""
+    import torch
+    buf = torch.full((PAD + off + B * T + PAD + 16,), SENTINEL, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()  # (the fill is done before the library's stream writes the rows)
+    assert buf.data_ptr() % 128 == 0
+    out = buf[PAD + off: PAD + off + B * T].view(B, T)
+    assert out.data_ptr() == buf.data_ptr() + 8 * (PAD + off) and out.is_contiguous()
+    return buf, out
+
+
+def rows_and_canaries(buf, B, T, off):
+    """The rows the library wrote; asserts that every sentinel around them is bitwise unchanged."""
+    import torch
+    torch.cuda.synchronize()
+    h = buf.cpu().numpy()
+    bits = np.array(SENTINEL).view(np.uint64)
+    lo, hi = PAD + off, PAD + off + B * T
+    before, after = h[:lo].view(np.uint64), h[hi:].view(np.uint64)
+    assert before.size >= PAD and after.size >= PAD
+    assert (before == bits).all(), ("before", off, np.flatnonzero(before != bits) - lo)
+    assert (after == bits).all(), ("after", off, np.flatnonzero(after != bits))
+    return h[lo:hi].reshape(B, T).copy()
+
+
+_UTTERANCES = {}
+
+
+def oracle_utterances(oracle, frames, hop, seeds):
+    key = (frames.shape, hop, tuple(int(s) for s in seeds))
+    if key not in _UTTERANCES:
+        _UTTERANCES[key] = np.stack([oracle.utterance(frames[u], hop, int(seeds[u]), FS)
+                                     for u in range(frames.shape[0])])
+    return _UTTERANCES[key]
+
+
+def check_device_rows(ctx, oracle, frames, hop, seeds, label, want=None):
+    """afs_synthesize into device rows at every offset of OFFSETS: bitwise the audio of a host
+    buffer, within GOLD_TOL of the oracle (want: its audio, if not one utterance per row), canaries."""
+    B, F = frames.shape
+    T = (F - 1) * hop
+    host = ctx.synthesize(frames, hop, seeds=seeds)
+    assert host.shape == (B, T) and np.isfinite(host).all()
+    if want is None:
+        want = oracle_utterances(oracle, frames, hop, seeds)
+    err = float(np.abs(host - want).max())
+    print(f"{label} T={T}: max |gpu - oracle| {err:.3e}")
+    assert err <= GOLD_TOL, (label, T, err)
+    for off in OFFSETS:
+        buf, out = device_out(B, T, off)
+        ctx.synthesize(frames, hop, seeds=seeds, out=out)
+        got = rows_and_canaries(buf, B, T, off)
+        assert np.array_equal(got, host), (label, T, off, float(np.abs(got - host).max()))
+
+
+# (F, hop): one transition of 47 samples in hop mode; rows of 66 with a frame change inside
+ROW_CASES = ((2, 47), (3, 33))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_device_output_alignment_and_canaries(contexts, oracle, solver):
+    """5 utterances with rows of odd length (47, 66 doubles) written to device memory 0, 1, 9 and 15
+    doubles past a 128-byte line: K1 stores whole lines through a window whose lanes are picked by
+    the row's position in its line (o_line), so every row starts and ends at a different lane; the
+    audio equals that of a host buffer bit for bit (the same kernels run) and no double outside the
+    rows changes."""
+    B = 5
+    seeds = np.arange(31, 31 + B, dtype=np.uint32)
+    for F, hop in ROW_CASES:
+        frames = np.ascontiguousarray(voice_frames(oracle, B)[:, :F])
+        check_device_rows(contexts(solver), oracle, frames, hop, seeds, solver)
+
+
+def test_device_output_alignment_one_wave_kernel(contexts, oracle):
+    """The one-wave kernel's copy of the window code (64 lanes, 1025 utterances, rows of 47)."""
+    ctx = contexts("tree64")
+    B = 1025
+    assert ctx.synthesis_kernel(B) == "tree_synth_kernel"
+    frames = np.ascontiguousarray(voice_frames(oracle, B)[:, :2])
+    n = len(VOICES)
+    seeds = (41 + np.arange(B) % n).astype(np.uint32)  # (utterance u plays as utterance u % n: n oracle runs)
+    want = oracle_utterances(oracle, frames[:n], 47, seeds[:n])[np.arange(B) % n]
+    check_device_rows(ctx, oracle, frames, 47, seeds, "tree64 x 1025", want=want)
+
+
+@pytest.mark.parametrize("solver", TREE_SOLVERS)
+def test_device_output_alignment_split_launches(oracle, solver, monkeypatch):
+    """Launches of 17 samples (AFS_LAUNCH_SAMPLES): each starts one double further into its line than
+    the one before, so launches begin at every alignment inside the device rows, and the pressure
+    rows move with them (p25_row0)."""
+    from areafunctionsynthesis_amd.synthesizer import Context
+    monkeypatch.setenv("AFS_LAUNCH_SAMPLES", "17")
+    ctx = Context(FS, solver="tree", lanes=LANES[solver], profile=True)
+    try:
+        B = 5
+        seeds = np.arange(31, 31 + B, dtype=np.uint32)
+        for F, hop in ROW_CASES:
+            frames = np.ascontiguousarray(voice_frames(oracle, B)[:, :F])
+            ctx.kernel_times()
+            check_device_rows(ctx, oracle, frames, hop, seeds, solver + " launches of 17")
+            assert ctx.kernel_times()["synth_launches"] == (1 + len(OFFSETS)) * -(-(F - 1) * hop // 17)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_session_device_output_alignment(contexts, oracle, solver):
+    """afs_session_synthesize with a device `out` 3 doubles past a line, calls of 17, 1 and 33
+    samples (rows shorter than a line; one sample; the hop-record kernel): the audio of a session
+    with host buffers bit for bit, within GOLD_TOL of the oracle's calls, canaries."""
+    from areafunctionsynthesis_amd import _native
+    from areafunctionsynthesis_amd.synthesizer import Synthesizer
+    ctx = contexts(solver)
+    B, off, calls = 5, 3, (17, 1, 33)
+    frames = voice_frames(oracle, B)
+    seeds = np.arange(51, 51 + B, dtype=np.uint32)
+    syn = Synthesizer(ctx, B, seeds)
+    try:
+        syn.synthesize_signal_tds(frames[:, 0], 441)
+        host = [syn.synthesize_signal_tds(frames[:, k + 1], n).copy() for k, n in enumerate(calls)]
+    finally:
+        syn.close()
+    want = [[] for _ in calls]
+    for u in range(B):
+        o = oracle.create(FS, int(seeds[u]))
+        try:
+            oracle.call(o, frames[u, 0], 441)
+            for k, n in enumerate(calls):
+                want[k].append(oracle.call(o, frames[u, k + 1], n))
+        finally:
+            oracle.destroy(o)
+    lib = ctx._lib
+    h = ctypes.c_void_p()
+    _native.check(lib.afs_session_create(ctx.handle, B, seeds.ctypes.data, ctypes.byref(h)), ctx.handle,
+                  "afs_session_create")
+    try:
+        produced = ctypes.c_int32(-1)
+        f0 = np.ascontiguousarray(frames[:, 0], dtype=FRAME_DTYPE)  # (kept alive over the call)
+        _native.check(lib.afs_session_synthesize(h, f0.ctypes.data, 441, None, None, ctypes.byref(produced), None),
+                      ctx.handle, "session latch")
+        assert produced.value == 0
+        for k, n in enumerate(calls):
+            buf, out = device_out(B, n, off)
+            fk = np.ascontiguousarray(frames[:, k + 1], dtype=FRAME_DTYPE)
+            _native.check(lib.afs_session_synthesize(h, fk.ctypes.data, n, out.data_ptr(), None,
+                                                     ctypes.byref(produced), None), ctx.handle, "session")
+            assert produced.value == n
+            got = rows_and_canaries(buf, B, n, off)
+            assert np.array_equal(got, host[k]), (k, n, float(np.abs(got - host[k]).max()))
+            err = float(np.abs(got - np.stack(want[k])).max())
+            print(f"{solver} session call n={n}: max |gpu - oracle| {err:.3e}")
+            assert err <= GOLD_TOL, (k, n, err)
+    finally:
+        lib.afs_session_destroy(h)

@@ -103,6 +103,37 @@ def test_restatement_matches_reference_random_trajectories(oracle):
         assert np.array_equal(x, y, equal_nan=True), trial
 
 
+@pytest.mark.skipif(not os.path.exists("/root/reference/src/Backend"), reason="reference sources absent")
+@pytest.mark.parametrize("fs", [22050.0, 44100.0])
+def test_incremental_calls_vs_reference_varying_n(oracle, fs):
+    """The incremental entry (ao_synthesize_call, the expectation of the GPU session tests) with a
+    call length that changes on every call (oracle_lib.CALL_SCHEDULE: 1 .. 441 samples, 0 giving
+    one) and frames that change on every call, against the reference's synthesizeSignalTds: every
+    chunk and the final rand() call count bit for bit."""
+    from oracle_lib import CALL_SCHEDULE, RefLib, schedule_frames
+    ref = RefLib()
+    fr = schedule_frames(oracle)
+    seed = 12
+    h = oracle.create(fs, seed)
+    r = ref.create(fs, seed)
+    try:
+        r0 = int(ref.lib.afsref_rand_calls())
+        assert oracle.call(h, fr[0], 441).size == 0 and ref.call(r, fr[0], 441).size == 0  # the latch
+        total = 0
+        for k, n in enumerate(CALL_SCHEDULE, start=1):
+            x = oracle.call(h, fr[k], n)
+            y = ref.call(r, fr[k], n)
+            assert x.shape == y.shape == (max(n, 1),), (k, n)
+            assert np.isfinite(x).all() and np.array_equal(x, y), (k, n)
+            total += x.size
+        assert total == 844
+        draws = oracle.rng_calls(h)
+        assert draws > 0 and draws == int(ref.lib.afsref_rand_calls()) - r0
+    finally:
+        oracle.destroy(h)
+        ref.destroy(r)
+
+
 OPTION_VARIANTS = [
     {"turbulence_losses": 0}, {"soft_walls": 0}, {"generate_noise_sources": 0},
     {"radiation_from_skin": 0}, {"piriform_fossa": 1}, {"inner_length_corrections": 0},
