@@ -178,7 +178,6 @@ afs_status run_chunks(afs_ctx *c, const afs_frame *frames, int64_t fstride, int 
     // (stride and base congruent to the output's modulo 16 doubles): K1 stores both through one
     // line-aligned window (tree_kernel.h).
     auto p25_for = [&](int64_t per, int64_t *stride) -> afs_status {
-      if (AFS_TONE_K6 != 1) return AFS_OK;  // (the tone filter in K1: no pressures stored)
       *stride = per + ((ostride - per) % 16 + 16) % 16;
       return ensure(c, &c->p25, &c->p25_bytes, ((size_t)B * (size_t)*stride + 32) * sizeof(double));
     };
@@ -207,7 +206,7 @@ afs_status run_chunks(afs_ctx *c, const afs_frame *frames, int64_t fstride, int 
       prof_pair(c, e1, e2, 0);
       // K6: the glottal-tone filter and the output stage of the launch's samples
       HIP_TRY(c, afs::launch_tree_output(c->dev_tab, (double *)ws, out + s0, ostride, s1 - s0, B,
-                                         AFS_TONE_K6 == 1 ? p25_row0(s0) : nullptr, p25_stride,
+                                         p25_row0(s0), p25_stride,
                                          c->cfg.options.radiation_from_skin, c->stream, skip, skip_cap));
       prof_pair(c, e2, prof_event(c), 2);
       return AFS_OK;

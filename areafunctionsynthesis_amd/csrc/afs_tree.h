@@ -53,9 +53,9 @@ struct TreeArgs {
   const uint32_t *skip_claims = nullptr;
   int64_t skip_cap = 0;
   // wave pairs: when the STAT waves run at a higher issue priority than their SIMDs' DYN waves
-  // (s_setprio; tree_core.h pair_prio): 0 never, 1 during the solver, 2 during the first phase group and
-  // the solver, 3 the whole launch (afs_capi.cpp picks by the launch's rounds of workgroups per CU
-  // slot; profiles/r06_pair_ab.txt r06zh-r06zm)
+  // (s_setprio; tree_core.h sample_step_pair): 0 never, 1 during the solver, 2 during the first
+  // phase group and the solver, 3 the whole launch (afs_capi.cpp picks by the launch's rounds of
+  // workgroups per CU slot; profiles/r06_pair_ab.txt r06zh-r06zm)
   int stat_prio = 0;
 };
 // K5: the noise-source plans of samples [s_begin, s_end) of `rows` frame rows.
@@ -95,16 +95,13 @@ inline int64_t plan_work_bytes(int64_t rows, int64_t slots) { return (rows * slo
 // 1: the throughput kernel as wave pairs (tree_kernel.h tree_pair_body): two waves per SIMD, the
 // phases of each four utterances split between a DYN and a STAT wave -- +8.7 % at 8192 static
 // vowels, the audio bitwise the same (profiles/r06_pair_ab.txt); 0: one wave per SIMD running every
-// phase (tree_synth_body; A/B builds)
+// phase (tree_synth_body: the bitwise check of the pairs).  It only chooses which kernels
+// tds_tree.hip instantiates and launches and the name afs_capi.cpp reports.
 #define AFS_PAIR 1
 #endif
-#ifndef AFS_TONE_K6
-// 1: K1 stores section 25's pressure per sample and K6 runs the glottal-tone filter over it
-// (+0.5 % end to end in round 3, profiles/r03ai_ab.txt); 0: K1 runs the filter itself, per sample
-// (A/B builds); 2: K1 runs it over each 16-sample output window when the window is stored, the tone
-// added to the stored flows (tree_kernel.h tone_window; A/B builds)
-#define AFS_TONE_K6 1
-#endif
+// The glottal-tone filter: K1 stores section 25's pressure per sample and K6 runs the filter over
+// it (+0.5 % end to end in round 3 against the filter in K1 per sample, profiles/r03ai_ab.txt; in
+// K1 per 16-sample output window, bitwise the same audio, -3.0 %, profiles/r06c_tone_window_ab.txt).
 #ifndef AFS_TREE_WPB
 // waves per block of the throughput kernel: 2 (8 utterances, 78 KB of LDS: two blocks per CU).  With
 // the slot order by shape, finer blocks balance the compute units' two rounds better: +0.6 % static
@@ -118,15 +115,13 @@ constexpr int TREE_W = AFS_TREE_W;      // lanes per utterance of the throughput
 constexpr int TREE_WPB = AFS_TREE_WPB;  // its waves per block
 constexpr int TREE_VOICE_W = 64;        // lanes per utterance of the voice kernel (one utterance per wave)
 // Batches up to this many utterances run the voice kernel as wave pairs (AFS_PAIR builds: two waves
-// per utterance on two SIMDs, 256 VGPRs each with the lean solver, so that a SIMD can hold two):
+// per utterance on two SIMDs, 256 VGPRs each with the lean solver, so that a SIMD can hold two; the
+// full solver takes 282 and a SIMD to each wave):
 // one voice's 1102-sample call 5.0 instead of 6.4 ms, config 2 (1024 utterances) +4.4 %, the audio
 // bitwise the one-wave kernel's (profiles/r06_pair_ab.txt r06z / r06za).  Larger batches that still
 // take 64 lanes (AFS_LANES_64) run one wave per utterance.
 #ifndef AFS_PAIR64_MAX
 #define AFS_PAIR64_MAX 1024
-#endif
-#ifndef AFS_PAIR64_WAVES
-#define AFS_PAIR64_WAVES 2  // waves per SIMD the voice pairs' registers must allow (1: the full solver, 282 VGPRs)
 #endif
 constexpr int TREE_PAIR64_MAX = AFS_PAIR64_MAX;
 constexpr int TREE_UPB = (64 / TREE_W) * TREE_WPB;  // utterances per block of the throughput kernel

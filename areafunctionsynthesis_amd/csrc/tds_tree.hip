@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(256, 2) tree_pair_kernel(TreeArgs a) {
 }
 // the voice kernel's pairs: two waves per utterance, each may take a whole SIMD's registers
 template <int MODEL, bool HOPS>
-__global__ void __launch_bounds__(128, AFS_PAIR64_WAVES) tree_pair64_kernel(TreeArgs a) {
+__global__ void __launch_bounds__(128, 2) tree_pair64_kernel(TreeArgs a) {
   __shared__ WaveLdsT<64> lds;
   tree_pair64_body<MODEL, HOPS>(a, lds);
 }

@@ -52,32 +52,6 @@ using std::fma;
 #define AFS_LDS_DRAIN() ((void)0)
 #endif
 
-// AFS_RNG_AHEAD = 2: rng_ahead keeps at least two blocks (60 values) of the rand() stream
-// pending, in a 128-entry prefix-sum ring, so that a sample with up to five active dipoles (the
-// usual four: the glottis source and a tongue constriction, two each) draws without generating
-// on the noise phase's chain; 1: one block ahead in a 64-entry ring (rounds 2-5).
-#ifndef AFS_RNG_AHEAD
-#define AFS_RNG_AHEAD 2
-#endif
-// AFS_ARM_SCAN = 1: the arm solver's lane-to-lane reduction and back substitution as prefix
-// scans (solve_arms); 0: one DPP step per lane of the longest arm (rounds 2-5)
-#ifndef AFS_ARM_SCAN
-#define AFS_ARM_SCAN 1
-#endif
-// AFS_WALK_PRESCALED = 1: the arm walk stores Y / d, F / d, E / d for the back substitution
-// (arm_back, which needs AFS_BACK_SCALED) instead of 1 / d, Y, F, E
-#ifndef AFS_WALK_PRESCALED
-#define AFS_WALK_PRESCALED 1
-#endif
-// AFS_JUNCTION_ADJ = 1: the junction triangle solved by its adjugate (solve_arms)
-#ifndef AFS_JUNCTION_ADJ
-#define AFS_JUNCTION_ADJ 1
-#endif
-// AFS_BACK_SCALED = 1: a lane's back substitution with its x-independent terms scaled ahead (arm_back)
-#ifndef AFS_BACK_SCALED
-#define AFS_BACK_SCALED 1
-#endif
-
 namespace afs {
 namespace tree {
 
@@ -120,21 +94,18 @@ enum : int {
   X_PREVFLOW = X_OUTF + 16,
   X_NONFIN = X_PREVFLOW + 1,
   X_NDRAW = X_NONFIN + 1,      // rand() calls so far (u64; diagnostics: afs_rng_draws)
-  X_RNG = X_NDRAW + 1,         // rand(): value ring (64 u32), prefix-sum ring (128 / 64 u32)
-  X_GP = X_RNG + (AFS_RNG_AHEAD >= 2 ? 96 : 64),  // interpolated glottis controls (6), 2 spare
+  X_RNG = X_NDRAW + 1,         // rand(): value ring (64 u32), prefix-sum ring (128 u32)
+  X_GP = X_RNG + 96,           // interpolated glottis controls (6), 2 spare
   X_RNG_SINK = X_GP + 6,       //   (spare: the sink of rng_ahead's idle stores, outside the solver arrays)
   X_TGLOT = X_GP + 8,          // transglottal-pressure filter x1..x4, y1..y4 (variable entrance loss)
   X_TVEL = X_TGLOT + 8,        // transvelar coupling filters H1, H2: x1..x4, y1..y4 each
   X_TVP = X_TVEL + 16,         // p[43], p[67] after the last update (transvelar filter inputs)
   X_RRAD = X_TVP + 2,          // mouth radiation R and L (section 64), from the network phase
-#if AFS_PAIR
+  // (the same layout for the one-wave kernel, which carries the pairs' slots through unchanged: one
+  // saved image, and the CPU emulators of both steps compile the same header)
   X_RELX2 = X_RRAD + 2,        // wave pairs: the glottis displacements' second buffer (sample_step_pair)
   X_RNGHP = X_RELX2 + 4,       // wave pairs: the rand() ring head and pending count (two int32)
-  X_AGLOT = X_RNGHP + 1,       // wave pairs: the upper glottis section's area of this sample (DYN -> STAT)
-  X_TOTAL = X_AGLOT + 1,
-#else
-  X_TOTAL = X_RRAD + 2,
-#endif
+  X_TOTAL = X_RNGHP + 2,       // (1 spare: the size of the saved image stays what it was)
   // LDS stride of the utterance blocks: 128 B modulo the 256-B bank row, so that the two
   // utterances of a 32-lane LDS lane group (ds_read_b64: lanes 0-31, 32-63) address the
   // same slot through disjoint banks
@@ -151,7 +122,6 @@ enum : int {
   PH_P1WAIT, PH_P2WAIT, PH_P3WAIT, PH_P4WAIT, PH_RNGP, PH_TAIL,
   PH_S_GLOT, PH_S_TGT,  // (the STAT wave's first phase group: the glottis and static network; the targets)
   PH_D_GEO,             // (the DYN wave's interpolation and glottis)
-  PH_P0WAIT,            // (the wait at the barrier inside the first phase group, AFS_PAIR_SPLIT1)
   PH_PLACE_HW, PH_PLACE_T0, PH_PLACE_T1,  // (not timed: the pair kernel's wave placement and loop span)
   PH_COUNT
 };
@@ -196,7 +166,7 @@ struct ArmCarry {
   double e28, e29;    // fossa lane: edges 84-28, 84-29
   double xJ;          // last lanes: the solution of their junction node (then the anchor's)
   double jd[3], jy[3], je[3], xj[3];  // junction lane: triangle pivots, rhs, edges, solutions
-  double sm[4];       // AFS_ARM_SCAN: the lane's segment of the pivot recurrence (2x2), then of the rhs / solution
+  double sm[4];       // the lane scans: the lane's segment of the pivot recurrence (2x2), then of the rhs / solution
   int sf, sb, end;    // the arm steps this lane reduces in (forward) / solves in (back), -1: none
   bool neg;           // a pivot this lane met was negative (the system is not positive definite)
 };
@@ -580,8 +550,8 @@ AFS_HD inline void rng_seed(int32_t *r, uint32_t seed) {
 // and in the lane registers (Lane::rhead, Lane::rpend, the same on every lane of the utterance:
 // no LDS round trip before the noise phase's addresses) the sequence number mod RNG_SRING of the
 // next value to generate and how many generated values have not been drawn yet (rng_ahead).
-// (AFS_RNG_AHEAD: see the top of this file)
-constexpr int RNG_RING = 64, RNG_SRING = AFS_RNG_AHEAD >= 2 ? 128 : 64;
+// (128 prefix sums: rng_ahead keeps two blocks pending)
+constexpr int RNG_RING = 64, RNG_SRING = 128;
 constexpr int RNG_R = 0, RNG_S = RNG_RING;
 static_assert((RNG_S + RNG_SRING) / 2 == X_GP - X_RNG, "the rand() region of the LDS block");
 // values per generation block: 3 residue chains x min(W, 10) lanes (<= 30 keeps every
@@ -882,27 +852,6 @@ AFS_HD inline GlotRes glottis_eval_split(const GlotIn &in, const CT &C, double r
   return res;
 }
 
-// The upper mass's area of the triangular glottis this sample (go.a1 of glottis_eval_split: the
-// same operations on its inputs), for the wave pairs' STAT wave, which needs no more of the glottis
-// (AFS_PAIR_SPLIT1=2).
-AFS_HD inline double glottis_upper_area(const GlotIn &in, double ratio) {
-  const double r1 = 1.0 - ratio;
-  double g0, g3, g4;
-  {
-#pragma clang fp contract(off)
-    g0 = r1 * in.fl[0] + ratio * in.fr[0];
-    g3 = r1 * in.fl[3] + ratio * in.fr[3];
-    g4 = r1 * in.fl[4] + ratio * in.fr[4];
-  }
-  const double chink = nonneg(g4);
-  const double q = glottis_q(g0);
-  const double f = fast_sqrt(q);
-  const double cord = G_REST_LEN * f;
-  double olen, clen, ow, cz;
-  glottis_open_close_one(g3, cord, in.rel[1], olen, clen, ow, cz);
-  return clampA_num(olen * ow + chink);
-}
-
 // The glottis state of the sample: new displacements, interpolated controls (X_GP + 1, the lung
 // pressure, is the row phase's source term of section 0).
 AFS_HD inline void glottis_commit(double *X, const GlotRes &r, int relx = X_RELX) {
@@ -1126,7 +1075,25 @@ enum : int { NZ_FULL = 0, NZ_T1ALL = 1, NZ_TONGUE1 = 2, NZ_GLOTTIS = 3, NZ_COUNT
 #ifndef AFS_NZ_SET
 #define AFS_NZ_SET 3
 #endif
-#define AFS_NZ_T1ALL ((AFS_NZ_SET & 4) != 0)
+constexpr bool nz_compiled(int nz) {
+  return nz == NZ_FULL || (nz == NZ_TONGUE1 && (AFS_NZ_SET & 1)) || (nz == NZ_GLOTTIS && (AFS_NZ_SET & 2)) ||
+         (nz == NZ_T1ALL && (AFS_NZ_SET & 4));
+}
+// f(std::integral_constant<int, NZ>{}) for the run-time variant nz (wave-uniform), over the compiled
+// variants alone (only they are instantiated; any other nz runs NZ_FULL, which serves everything)
+template <class F>
+AFS_HD inline void with_noise_variant(int nz, F f) {
+  if constexpr (nz_compiled(NZ_GLOTTIS)) {
+    if (nz == NZ_GLOTTIS) return f(std::integral_constant<int, NZ_GLOTTIS>{});
+  }
+  if constexpr (nz_compiled(NZ_TONGUE1)) {
+    if (nz == NZ_TONGUE1) return f(std::integral_constant<int, NZ_TONGUE1>{});
+  }
+  if constexpr (nz_compiled(NZ_T1ALL)) {
+    if (nz == NZ_T1ALL) return f(std::integral_constant<int, NZ_T1ALL>{});
+  }
+  f(std::integral_constant<int, NZ_FULL>{});
+}
 template <int W, int NZ>
 struct NoiseV {
   static constexpr int NC = NZ == NZ_FULL ? 4 : (NZ == NZ_GLOTTIS ? 1 : 2);
@@ -1413,14 +1380,15 @@ AFS_HD inline void rng_block2(Xc &x, uint32_t *g, uint32_t *sink, int head, bool
 }
 
 // The rand() stream generated ahead of its use, so that the noise phase of the next sample
-// finds its draws generated: AFS_RNG_AHEAD = 2: two blocks (rng_block2) whenever fewer than two
-// blocks are pending (up to five active sources, 60 draws; the usual four -- the glottis source
-// and a tongue constriction, two dipoles each -- draw 48); 1: one block whenever fewer than one
-// is pending (one or two active sources).  A sample that needs more generates further blocks in
+// finds its draws generated: two blocks (rng_block2) whenever fewer than two blocks are pending,
+// in the 128-entry prefix-sum ring (up to five active sources, 60 draws; the usual four -- the
+// glottis source and a tongue constriction, two dipoles each -- draw 48, without generating on the
+// noise phase's chain; rounds 2-5 kept one block ahead in a 64-entry ring: one or two active
+// sources).  A sample that needs more generates further blocks in
 // the noise phase.  It depends on the ring alone, not on the acoustic state, so it runs in the
 // update block after the solver, beside the update's own chains instead of on the noise
-// phase's.  With fewer than AFS_RNG_AHEAD blocks pending, the values and prefix sums a
-// generation overwrites (rng_block, rng_block2) are no longer needed: neither the pending ones,
+// phase's.  With fewer than two blocks pending, the values and prefix sums a
+// generation overwrites (rng_block2) are no longer needed: neither the pending ones,
 // the prefix sum before the oldest of them, nor the generator's 31-value history.  Draws are
 // counted when consumed (phase_noise), so the rand() call count is the reference's.
 #ifndef AFS_RNG_SKIP
@@ -1429,16 +1397,13 @@ AFS_HD inline void rng_block2(Xc &x, uint32_t *g, uint32_t *sink, int head, bool
 template <int W, class Xc>
 AFS_HD inline void rng_ahead(Xc &x, double *X) {
   constexpr int RNG_BLOCK = 3 * rng_lanes<W>();
-  constexpr int GEN = AFS_RNG_AHEAD >= 2 ? 2 * RNG_BLOCK : RNG_BLOCK;  // values per generation
+  constexpr int GEN = 2 * RNG_BLOCK;  // values per generation
   static_assert(GEN <= RNG_SRING - GEN, "pending values (< GEN), the prefix sum before them and a generation fit the ring");
   static_assert(GEN <= RNG_RING, "a generation fits the value ring");
   uint32_t *g = (uint32_t *)(X + X_RNG);
   const int head = x.first().rhead, pend = x.first().rpend;
   const bool gen = pend < GEN;
-  if (!AFS_RNG_SKIP || x.wave_any(gen)) {
-    if constexpr (AFS_RNG_AHEAD >= 2) rng_block2<W>(x, g, (uint32_t *)(X + X_RNG_SINK), head, gen);
-    else rng_block<W>(x, g, (uint32_t *)(X + X_RNG_SINK), head, gen);
-  }
+  if (!AFS_RNG_SKIP || x.wave_any(gen)) rng_block2<W>(x, g, (uint32_t *)(X + X_RNG_SINK), head, gen);
   x.par([&](int gl, Lane<W> &R) {
     (void)gl;
     R.rhead = gen ? ((head + GEN) & (RNG_SRING - 1)) : head;
@@ -1656,18 +1621,11 @@ AFS_HD inline void arm_walk(const ArmRec &rr, double *X, ArmCarry &a) {
     yA = fma(-g, Y[p], yA);
     D[p + 1] = fma(-e2, inv, D[p + 1]);
     Y[p + 1] = fma(-h, Y[p], Y[p + 1]);
-#if AFS_WALK_PRESCALED
     // the back substitution's factors, scaled by the pivot's reciprocal here (g and h are needed
     // anyway): x_p = Y_p / d_p - (F_p / d_p) xA - (E_p / d_p) x_{p+1} (arm_back)
     xat(X, r.d[p] + RHS_DELTA) = Y[p] * inv;
     xat(X, r.u[p]) = g;
     xat(X, r.e[p]) = h;
-#else
-    xat(X, r.d[p]) = inv;                // factors for the back substitution
-    xat(X, r.d[p] + RHS_DELTA) = Y[p];
-    xat(X, r.u[p]) = F;
-    xat(X, r.e[p]) = E[p];
-#endif
     F = -(g * E[p]);                     // fill edge anchor - p+1
   }
 #pragma unroll
@@ -1686,11 +1644,10 @@ AFS_HD inline void arm_walk(const ArmRec &rr, double *X, ArmCarry &a) {
 AFS_HD inline void arm_back(const ArmRec &rr, const ArmJunction &J, bool junction, double *X, const ArmCarry &a,
                             double xA) {
   const ArmRec r = rr;
-  double inv[ARM_P - 1], y[ARM_P - 1], Fp[ARM_P - 1], Ep[ARM_P - 1];
+  double y[ARM_P - 1], Fp[ARM_P - 1], Ep[ARM_P - 1];  // (the walk's Y / d, F / d, E / d)
   double il[ARM_FOLDS], yl[ARM_FOLDS], l0[ARM_FOLDS], l1[ARM_FOLDS];
 #pragma unroll
   for (int p = 0; p < ARM_P - 1; ++p) {
-    inv[p] = AFS_WALK_PRESCALED ? 1.0 : xat(X, r.d[p]);  // (prescaled: Y / d, F / d, E / d)
     y[p] = xat(X, r.d[p] + RHS_DELTA);
     Fp[p] = xat(X, r.u[p]);
     Ep[p] = xat(X, r.e[p]);
@@ -1704,28 +1661,16 @@ AFS_HD inline void arm_back(const ArmRec &rr, const ArmJunction &J, bool junctio
   }
   double xs[ARM_P];
   xs[ARM_P - 1] = a.x;
-#if AFS_BACK_SCALED
   // x_p = (y_p - F_p xA - E_p x_{p+1}) / d_p with the terms that do not depend on x_{p+1} scaled
-  // ahead: one fma per position on the chain instead of three dependent operations
+  // ahead (by the walk): one fma per position on the chain instead of three dependent operations
   double c[ARM_P - 1], e[ARM_P - 1];
 #pragma unroll
   for (int p = 0; p < ARM_P - 1; ++p) {
-    if constexpr (AFS_WALK_PRESCALED) {
-      c[p] = fma(-Fp[p], xA, y[p]);
-      e[p] = -Ep[p];
-    } else {
-      c[p] = fma(-Fp[p], xA, y[p]) * inv[p];
-      e[p] = -Ep[p] * inv[p];
-    }
+    c[p] = fma(-Fp[p], xA, y[p]);
+    e[p] = -Ep[p];
   }
 #pragma unroll
   for (int p = ARM_P - 2; p >= 0; --p) xs[p] = fma(e[p], xs[p + 1], c[p]);
-#else
-#pragma unroll
-  for (int p = ARM_P - 2; p >= 0; --p) {
-    xs[p] = fma(-Fp[p], xA, fma(-Ep[p], xs[p + 1], y[p])) * inv[p];
-  }
-#endif
 #pragma unroll
   for (int p = 0; p < ARM_P; ++p) xat(X, r.u[p]) = xs[p];
 #pragma unroll
@@ -1739,8 +1684,9 @@ AFS_HD inline void arm_back(const ArmRec &rr, const ArmJunction &J, bool junctio
   xat(X, junction ? J.u[2] : sink) = a.xj[2];
 }
 
-// The same walk and back substitution with the loads issued two positions ahead instead of all
-// ahead (wave pairs, sample_step_pair: the pair's kernel must fit 256 registers).  The record's
+// The same walk and back substitution with the loads issued one position ahead instead of all
+// ahead (two positions ahead measured -2 %, r06_pair_ab.txt; wave pairs, sample_step_pair: the
+// pair's kernel must fit 256 registers).  The record's
 // offsets come into registers first (no LDS round trip for an address on the chain), and every
 // value is computed by the same operations in the same order as arm_walk / arm_back: a fold's terms
 // on positions q, q + 1 (its part on q -- pivot, rhs and the edge q - q+1 -- before the walk's step
@@ -1768,9 +1714,6 @@ AFS_HD inline ArmRaw arm_raw(const ArmRec &r, const double *X, int q) {
   }
   return v;
 }
-#ifndef AFS_ARM_AHEAD
-#define AFS_ARM_AHEAD 1  // positions the lean walk / back substitution load ahead (1 or 2: -2 %, r06_pair_ab.txt)
-#endif
 AFS_HD inline void arm_walk_lean(const ArmRec &rr, double *X, ArmCarry &a) {
   const ArmRec r = rr;
   bool neg = false;
@@ -1779,13 +1722,12 @@ AFS_HD inline void arm_walk_lean(const ArmRec &rr, double *X, ArmCarry &a) {
   a.e28 = xat(X, r.fx0);
   a.e29 = xat(X, r.fx1);
   a.ej = xat(X, r.ej);
-  ArmRaw c = arm_raw(r, X, 0), n1 = AFS_ARM_AHEAD >= 2 ? arm_raw(r, X, 1) : ArmRaw{};
+  const ArmRaw c = arm_raw(r, X, 0);
   double Dc = c.D, Yc = c.Y, Ec = c.E;
   double F = 0.0, dA = 0.0, yA = 0.0;
 #pragma unroll
   for (int p = 0; p < ARM_P - 1; ++p) {
-    if (AFS_ARM_AHEAD < 2) n1 = arm_raw(r, X, p + 1);
-    const ArmRaw n2 = AFS_ARM_AHEAD >= 2 ? arm_raw(r, X, p + 2) : ArmRaw{};
+    const ArmRaw n1 = arm_raw(r, X, p + 1);
     double Dn = n1.D, Yn = n1.Y, En = n1.E;
     const int fp = arm_fold_at(p), fn = arm_fold_at(p + 1);
     if (fp >= 0) {  // the fold at p: its part on p + 1
@@ -1819,7 +1761,6 @@ AFS_HD inline void arm_walk_lean(const ArmRec &rr, double *X, ArmCarry &a) {
     Dc = Dn;
     Yc = Yn;
     Ec = En;
-    n1 = n2;
   }
 #pragma unroll
   for (int f = 0; f < ARM_FOLDS; ++f) xat(X, r.ld[f]) = il[f];
@@ -1855,26 +1796,20 @@ AFS_HD inline ArmRawB arm_raw_back(const ArmRec &r, const double *X, int p) {
 }
 AFS_HD inline void arm_back_lean(const ArmRec &rr, const ArmJunction &J, bool junction, double *X, const ArmCarry &a,
                                  double xA) {
-  static_assert(AFS_WALK_PRESCALED && AFS_BACK_SCALED, "the lean back substitution is the prescaled, scaled form");
   const ArmRec r = rr;
   double xn = a.x;  // x_{p+1}
-  ArmRawB q1 = arm_raw_back(r, X, ARM_P - 2), q2 = AFS_ARM_AHEAD >= 2 ? arm_raw_back(r, X, ARM_P - 3) : ArmRawB{};
+  ArmRawB q1 = arm_raw_back(r, X, ARM_P - 2);
   xat(X, r.u[ARM_P - 1]) = xn;
 #pragma unroll
   for (int p = ARM_P - 2; p >= 0; --p) {
-    const ArmRawB q3 = AFS_ARM_AHEAD >= 2 ? arm_raw_back(r, X, p - 2) : arm_raw_back(r, X, p - 1);
+    const ArmRawB q2 = arm_raw_back(r, X, p - 1);
     const double c = fma(-q1.Fp, xA, q1.y), e = -q1.Ep;
     const double xp = fma(e, xn, c);
     xat(X, r.u[p]) = xp;
     const int f = arm_fold_at(p);
     if (f >= 0) xat(X, r.lu[f]) = fma(-q1.l1, xn, fma(-q1.l0, xp, q1.yl)) * q1.il;
     xn = xp;
-    if (AFS_ARM_AHEAD >= 2) {
-      q1 = q2;
-      q2 = q3;
-    } else {
-      q1 = q3;
-    }
+    q1 = q2;
   }
   const uint32_t sink = (uint32_t)(X_U + U_SINK) * 8u;
   xat(X, junction ? J.u[0] : sink) = a.xj[0];
@@ -1920,9 +1855,9 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
       },
       [&](int, Lane<W> &R, const D4 &v) { R.ac.Db -= v.v[0]; R.ac.Yb -= v.v[1]; R.ac.F -= v.v[2]; });
   x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) { R.ac.neg = R.ac.neg | (R.ac.Db < 0.0); });
-#if AFS_ARM_SCAN
   // Arm reduction toward the junction as prefix scans over the lanes (three DPP steps each
-  // instead of ARM_MAXLEN - 1 dependent ones).  The boundary pivots follow d_k = D_k - F_k^2 /
+  // instead of ARM_MAXLEN - 1 dependent ones: one DPP step per lane of the longest arm, rounds
+  // 2-5).  The boundary pivots follow d_k = D_k - F_k^2 /
   // d_{k-1} (F_k: the lane's edge to the previous lane's boundary, 0 at an arm's first lane),
   // i.e. (n_k, m_k) = M_k (n_{k-1}, m_{k-1}), M_k = [[D_k, -F_k^2], [1, 0]], d_k = n_k / m_k: the
   // lanes scan the products of their M (an arm's first lane makes the ratio independent of the
@@ -1981,24 +1916,6 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
     if (q == 2) aff(std::integral_constant<int, 4>{});
   }
   x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) { R.ac.Yb = R.ac.sm[1]; });
-#else
-  // arm reduction toward the junction: in step s the lanes at position s of their arm
-  // eliminate the previous boundary (lane k-1) from their own
-  // (a lane off its step updates with a zero edge: no change, the same reciprocal again)
-  x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) { R.ac.inv = pivot_recip(R.ac.Db); });
-#pragma unroll
-  for (int s = 1; s < ARM_MAXLEN; ++s) {
-    x.template pull<-1, 2>([&](int, Lane<W> &R) { return D4{{R.ac.inv, R.ac.Yb, 0.0, 0.0}}; },
-                           [&](int, Lane<W> &R, const D4 &v) {
-                             const double Fs = (R.ac.sf == s) ? R.ac.F : 0.0;
-                             const double F2 = Fs * Fs, f = Fs * v.v[0];
-                             R.ac.Db = fma(-F2, v.v[0], R.ac.Db);
-                             R.ac.Yb = fma(-f, v.v[1], R.ac.Yb);
-                             R.ac.inv = pivot_recip(R.ac.Db);
-                           });
-  }
-  x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) { R.ac.neg = R.ac.neg | (R.ac.Db < 0.0); });
-#endif
   // the junction lane takes the three arms' last boundaries (pivot inverse, rhs, edge) and
   // solves the triangle: eliminate 65, then 41; solve 40 (uniform code on every lane)
   auto give = [&](int, Lane<W> &R) { return D4{{R.ac.inv, R.ac.Yb, R.ac.ej, 0.0}}; };
@@ -2012,7 +1929,6 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
   x.template pull<ARM_END_A - ARM_JUNCTION, 3>(give, take(0));
   x.template pull<ARM_END_B - ARM_JUNCTION, 3>(give, take(1));
   x.template pull<ARM_END_C - ARM_JUNCTION, 3>(give, take(2));
-#if AFS_JUNCTION_ADJ
   // the triangle's 3 x 3 SPD system by its adjugate: cofactors, determinant and the three
   // numerators side by side, one reciprocal (9 dependent operations instead of ~16 of the
   // elimination); not positive definite (the elimination's negative pivot) <=> d2, its 2 x 2
@@ -2030,30 +1946,6 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
     R.ac.xj[1] = fma(c01, y[0], fma(c11, y[1], c12 * y[2])) * r;
     R.ac.xj[2] = fma(c02, y[0], fma(c12, y[1], c22 * y[2])) * r;
   });
-#else
-  x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) {
-    double *d = R.ac.jd, *y = R.ac.jy;
-    double e01 = R.ac.je[0];
-    const double e02 = R.ac.je[1], e12 = R.ac.je[2];
-    const double i2 = pivot_recip(d[2]);
-    const double g0 = e02 * i2, g1 = e12 * i2;
-    d[0] = fma(-g0, e02, d[0]);
-    y[0] = fma(-g0, y[2], y[0]);
-    d[1] = fma(-g1, e12, d[1]);
-    y[1] = fma(-g1, y[2], y[1]);
-    e01 = fma(-g0, e12, e01);
-    const double i1 = pivot_recip(d[1]);
-    const double h = e01 * i1;
-    d[0] = fma(-h, e01, d[0]);
-    y[0] = fma(-h, y[1], y[0]);
-    const bool dneg = (d[0] < 0.0) | (d[1] < 0.0) | (d[2] < 0.0);
-    const double x0 = dneg ? NAN : y[0] * pivot_recip(d[0]);
-    const double x1 = fma(-e01, x0, y[1]) * i1;
-    R.ac.xj[0] = x0;
-    R.ac.xj[1] = x1;
-    R.ac.xj[2] = fma(-e12, x1, fma(-e02, x0, y[2])) * i2;
-  });
-#endif
   x.template pull<ARM_JUNCTION - ARM_END_A, 1>([&](int, Lane<W> &R) { return D4{{R.ac.xj[0], 0.0, 0.0, 0.0}}; },
                                                [&](int k, Lane<W> &R, const D4 &v) { if (k == ARM_END_A) R.ac.xJ = v.v[0]; });
   x.template pull<ARM_JUNCTION - ARM_END_B, 1>([&](int, Lane<W> &R) { return D4{{R.ac.xj[1], 0.0, 0.0, 0.0}}; },
@@ -2065,7 +1957,6 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
   // back along the arms
   x.template pull<1, 1>([&](int, Lane<W> &R) { return D4{{R.ac.F, 0.0, 0.0, 0.0}}; },
                         [&](int, Lane<W> &R, const D4 &v) { R.ac.Fn = v.v[0]; });
-#if AFS_ARM_SCAN
   // x_k = (Yb_k - Fn_k x_{k+1}) / d_k along an arm, x = (Yb - ej xJ) / d at its last lane: an
   // affine recurrence toward the arms' far ends, scanned (lanes past the row read zeros: the arms'
   // last lanes, the fossa and the junction lane have no successor term)
@@ -2089,19 +1980,6 @@ AFS_HD inline void solve_arms(Xc &x, double *X, const Consts &C) {
     if (q == 2) aff(std::integral_constant<int, 4>{});
   }
   x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) { R.ac.x = R.ac.sm[1]; });
-#else
-  x.lanes(TREE_CHAINS, [&](int, Lane<W> &R) {
-    R.ac.x = R.ac.end ? fma(-R.ac.ej, R.ac.xJ, R.ac.Yb) * R.ac.inv : 0.0;
-  });
-#pragma unroll
-  for (int s = ARM_MAXLEN - 2; s >= 0; --s) {
-    x.template pull<1, 1>([&](int, Lane<W> &R) { return D4{{R.ac.x, 0.0, 0.0, 0.0}}; },
-                          [&](int, Lane<W> &R, const D4 &v) {
-                            const bool on = R.ac.sb == s;
-                            R.ac.x = on ? fma(-R.ac.Fn, v.v[0], R.ac.Yb) * R.ac.inv : R.ac.x;
-                          });
-  }
-#endif
   // the fossa lane: 84 from 28 and 29
   x.template pull<ARM_L28 - ARM_FOSSA, 1>([&](int, Lane<W> &R) { return D4{{R.ac.x, 0.0, 0.0, 0.0}}; },
                                           [&](int, Lane<W> &R, const D4 &v) { R.ac.Fn = v.v[0]; });
@@ -2469,12 +2347,8 @@ AFS_HD inline void sample_step(Xc &x, double *X, const Uni &U, const Consts &C, 
   x.sync();
   x.mark(PH_TARGETS);
   if constexpr (NZ == NZ_DYN) {
-    (void)nz;
-    // (only the variants of AFS_NZ_SET are compiled; the CPU emulator compiles them all)
-    if ((AFS_NZ_SET & 2) && nz == NZ_GLOTTIS) targets_noise<W, NZ_GLOTTIS>(x, X, U, C, a_glot_up);
-    else if ((AFS_NZ_SET & 1) && nz == NZ_TONGUE1) targets_noise<W, NZ_TONGUE1>(x, X, U, C, a_glot_up);
-    else if ((AFS_NZ_SET & 4) && nz == NZ_T1ALL) targets_noise<W, NZ_T1ALL>(x, X, U, C, a_glot_up);
-    else targets_noise<W, NZ_FULL>(x, X, U, C, a_glot_up);
+    // (only the compiled variants; the CPU emulator compiles them all)
+    with_noise_variant(nz, [&](auto V) { targets_noise<W, decltype(V)::value>(x, X, U, C, a_glot_up); });
   } else {
     (void)a_glot_up;
     (void)nz;
@@ -2508,125 +2382,81 @@ AFS_HD inline void sample_step(Xc &x, double *X, const Uni &U, const Consts &C, 
 }
 
 
-// One sample on a wave pair (tree_kernel.h, AFS_PAIR): the wave of role ROLE runs its half of the
-// phases; the pair's waves meet at a workgroup barrier (x.bar()) between the four phase groups, so
-// LDS carries everything one wave writes and the other reads (the dynamic slots' L, R, E, D and the
-// static slots' D, the dipole samples, the rows, the solution, the published pressures and flows).
-//   P1  DYN: interpolation, the glottis and its commit, [barrier], the dynamic slots' network
-//       STAT: the static slots' D, [barrier], targets, noise
-//       (AFS_PAIR_SPLIT1=0: no barrier inside P1, both waves evaluate the glottis, STAT commits it)
+// One sample on a wave pair (tree_kernel.h): the wave of role ROLE runs its half of the phases; the
+// pair's waves meet at a workgroup barrier (x.bar()) between the four phase groups, so LDS carries
+// everything one wave writes and the other reads (the dynamic slots' L, R, E, D and the static
+// slots' D, the dipole samples, the rows, the solution, the published pressures and flows).
+//   P1  DYN: interpolation, the glottis, the dynamic slots' network
+//       STAT: the static slots' D, the glottis and its commit, targets, noise
+//       (no barrier inside P1: both waves evaluate the glottis, STAT commits it.  The glottis once,
+//       on DYN, with a fifth barrier measured -2.7 %; STAT evaluating only the upper area -1 %)
 //   P2  rows of each role's slots
-//   P3  STAT: the arm solver (lean form) and the rand() blocks ahead
+//   P3  STAT: the arm solver, in the lean form (the full form spills: -17 %)
+//       DYN: the rand() blocks ahead, beside the solver (on STAT after it: -4.5 %)
 //   P4  the state update of each role's slots; DYN: the radiated flow (R.sample)
+// (the measurements: profiles/AB_LOG.md, round 6, raw runs in profiles/r06_pair_ab.txt)
 // Both waves read the glottis displacements at the start of P1 and STAT commits the new ones in P1:
-// two buffers, sample parity par reads X_RELX (par 0) or X_RELX2 and writes the other.
-#if AFS_PAIR
-#ifndef AFS_PAIR_LEAN
-#define AFS_PAIR_LEAN 1  // the STAT wave's solver in the lean form (arm_walk_lean; 0: arm_walk, every load ahead)
-#endif
-#ifndef AFS_PAIR_PRIO
-// the STAT wave's issue priority over its SIMD's other wave (a DYN wave of another workgroup): 1 during
-// the solver, 2 during the first phase group and the solver, 3 always; 0: the launch's mode
-// (TreeArgs::stat_prio, the executor's prio) -- nonzero values fix it at compile time (A/B builds)
-#define AFS_PAIR_PRIO 0
-#endif
-template <class Xc> AFS_HD inline int pair_prio(const Xc &x) { return AFS_PAIR_PRIO ? AFS_PAIR_PRIO : x.prio; }
-#ifndef AFS_PAIR_SPLIT1
-// the first phase group in two: the DYN wave evaluates and commits the glottis alone (the STAT wave
-// its static network meanwhile), a barrier, then DYN's network beside STAT's targets and noise (0:
-// both waves evaluate the glottis, no barrier inside the group; 1 measured -2.7 %, r06_pair_ab.txt)
-#define AFS_PAIR_SPLIT1 0  // (2: DYN commits the glottis, STAT evaluates its upper area alone, no barrier)
-#endif
-#ifndef AFS_PAIR_RNG_DYN
-#define AFS_PAIR_RNG_DYN 1  // the rand() blocks ahead on the DYN wave during the solver (0: on the STAT wave after it)
-#endif
+// two buffers, sample parity par reads X_RELX (par 0) or X_RELX2 and writes the other.  The rand()
+// ring's head and pending count move on both waves (STAT draws, DYN generates): they travel through
+// X_RNGHP.
+// The STAT wave's issue priority over its SIMD's other wave (a DYN wave of another workgroup) follows
+// the launch's mode x.prio (TreeArgs::stat_prio, include/afs.h): 1 raised during the solver, 2 during
+// the first phase group and the solver, 3 for the whole launch (tree_pair_run), 0 never.
+// Scheduling barriers between the phase groups: the scheduler otherwise mixes their code and keeps
+// values of both live at once -- the pair kernel must fit 256 registers.
+template <int W, class Xc>
+AFS_HD inline void rng_ring_pos_load(Xc &x, const double *X) {
+  x.par([&](int gl, Lane<W> &R) {
+    (void)gl;
+    const int32_t *hp = (const int32_t *)(X + X_RNGHP);
+    R.rhead = hp[0];
+    R.rpend = hp[1];
+  });
+}
+template <int W, class Xc>
+AFS_HD inline void rng_ring_pos_store(Xc &x, double *X) {
+  x.par([&](int gl, Lane<W> &R) {
+    if (gl == 0) {
+      int32_t *hp = (int32_t *)(X + X_RNGHP);
+      hp[0] = R.rhead;
+      hp[1] = R.rpend;
+    }
+  });
+}
 template <int W, int MODEL, int NZ, int ROLE, bool VARLOSS, class Xc>
 AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par) {
   static_assert(ROLE == ROLE_DYN || ROLE == ROLE_STAT, "a wave pair's roles");
-// (scheduling barriers between the phase groups: the scheduler otherwise mixes their code and keeps
-// values of both live at once -- the pair kernel must fit 256 registers; with AFS_PAIR_MARKS named
-// markers in the assembly instead, for spill accounting)
-#if defined(AFS_PAIR_MARKS) && defined(__HIP_DEVICE_COMPILE__)
-#define AFS_PM(t) __asm__ volatile(t)
-#else
-#define AFS_PM(t) AFS_SCHED_BARRIER()
-#endif
-  AFS_PM(";MARK P1 begin");
-  if constexpr (ROLE == ROLE_STAT) {
-    if (pair_prio(x) == 2) AFS_SETPRIO(2);
-  }
+  constexpr bool STAT = ROLE == ROLE_STAT;
+  AFS_SCHED_BARRIER();
+  if (STAT && x.prio == 2) AFS_SETPRIO(2);
   const int rcur = par ? X_RELX2 : X_RELX, rnext = par ? X_RELX : X_RELX2;
-  // (SPLIT1 2: DYN commits the glottis, STAT evaluates only the upper area it needs -- the
-  // triangular model's split form; the two-mass model keeps both evaluations)
-  constexpr bool kSplitA = AFS_PAIR_SPLIT1 == 2 && MODEL == AFS_GLOTTIS_TRIANGULAR && Xc::kGlottisSplit;
-  constexpr bool kDynCommit = AFS_PAIR_SPLIT1 == 1 || kSplitA;
-  if constexpr (ROLE == ROLE_DYN) {
-    GlotRes g{};
-    x.par_uniform([&](int gl, Lane<W> &R) { phase_interpolate<W>(gl, R, X, C, ratio); },
-                  [&](Lane<W> &R) {
-                    (void)R;
-                    const double p4[4] = {X[X_P4 + 0], X[X_P4 + 1], X[X_P4 + 2], X[X_P4 + 3]};
-                    if constexpr (Xc::kGlottisSplit && MODEL == AFS_GLOTTIS_TRIANGULAR)
-                      g = glottis_eval_split(glottis_inputs(X, rcur), C, ratio, p4, x.half8(),
-                                             [&](double v) { return x.xch8(v); });
-                    else
-                      g = glottis_eval<MODEL>(glottis_inputs(X, rcur), C, ratio, p4);
-                    if constexpr (kDynCommit) glottis_commit(X, g, rnext);
-                    if constexpr (AFS_PAIR_SPLIT1 == 1) X[X_AGLOT] = g.go.a1;
-                  });
+  // the glottis of this sample (lane-uniform), beside the role's per-lane work
+  GlotRes g{};
+  auto glottis = [&](Lane<W> &R) {
+    (void)R;
+    const double p4[4] = {X[X_P4 + 0], X[X_P4 + 1], X[X_P4 + 2], X[X_P4 + 3]};
+    if constexpr (Xc::kGlottisSplit && MODEL == AFS_GLOTTIS_TRIANGULAR)
+      g = glottis_eval_split(glottis_inputs(X, rcur), C, ratio, p4, x.half8(), [&](double v) { return x.xch8(v); });
+    else
+      g = glottis_eval<MODEL>(glottis_inputs(X, rcur), C, ratio, p4);
+    if constexpr (STAT) glottis_commit(X, g, rnext);
+  };
+  if constexpr (!STAT) {
+    x.par_uniform([&](int gl, Lane<W> &R) { phase_interpolate<W>(gl, R, X, C, ratio); }, glottis);
     x.mark(PH_D_GEO);
-    if constexpr (AFS_PAIR_SPLIT1 == 1) {
-      x.bar();
-      x.mark(PH_P0WAIT);
-    }
     x.dyn_neighbors();
     x.par([&](int gl, Lane<W> &R) { phase_network<W, VARLOSS, ROLE_DYN>(gl, R, X, U, C, g.go); });
     x.mark(PH_NETWORK);
   } else {
-    double a_glot_up = 0.0;
-    if constexpr (AFS_PAIR_SPLIT1 == 1) {
-      x.par([&](int gl, Lane<W> &R) { phase_network<W, VARLOSS, ROLE_STAT>(gl, R, X, U, C, GlotOut{}); });
-      x.mark(PH_S_GLOT);
-      x.bar();
-      x.mark(PH_P0WAIT);
-      a_glot_up = X[X_AGLOT];
-    } else if constexpr (kSplitA) {
-      x.par_uniform([&](int gl, Lane<W> &R) { phase_network<W, VARLOSS, ROLE_STAT>(gl, R, X, U, C, GlotOut{}); },
-                    [&](Lane<W> &R) {
-                      (void)R;
-                      a_glot_up = glottis_upper_area(glottis_inputs(X, rcur), ratio);
-                    });
-      x.mark(PH_S_GLOT);
-    } else {
     x.par_uniform([&](int gl, Lane<W> &R) { phase_network<W, VARLOSS, ROLE_STAT>(gl, R, X, U, C, GlotOut{}); },
-                  [&](Lane<W> &R) {
-                    (void)R;
-                    const double p4[4] = {X[X_P4 + 0], X[X_P4 + 1], X[X_P4 + 2], X[X_P4 + 3]};
-                    GlotRes g;
-                    if constexpr (Xc::kGlottisSplit && MODEL == AFS_GLOTTIS_TRIANGULAR)
-                      g = glottis_eval_split(glottis_inputs(X, rcur), C, ratio, p4, x.half8(),
-                                             [&](double v) { return x.xch8(v); });
-                    else
-                      g = glottis_eval<MODEL>(glottis_inputs(X, rcur), C, ratio, p4);
-                    glottis_commit(X, g, rnext);
-                    a_glot_up = g.go.a1;
-                  });
+                  glottis);
     x.mark(PH_S_GLOT);
-    }
-    AFS_PM(";MARK targets");
-#if !defined(AFS_PAIR_PROBE_NONOISE)
-#if AFS_PAIR_RNG_DYN
-    x.par([&](int gl, Lane<W> &R) {  // (the ring's head and pending count, which the DYN wave's rng_ahead moved)
-      (void)gl;
-      const int32_t *hp = (const int32_t *)(X + X_RNGHP);
-      R.rhead = hp[0];
-      R.rpend = hp[1];
-    });
-#endif
-    x.par([&](int gl, Lane<W> &R) { phase_targets<W, NZ>(x, gl, R, X, C, a_glot_up); });
+    AFS_SCHED_BARRIER();
+    rng_ring_pos_load<W>(x, X);  // (which the DYN wave's rng_ahead moved)
+    x.par([&](int gl, Lane<W> &R) { phase_targets<W, NZ>(x, gl, R, X, C, g.go.a1); });
     x.sync();
     x.mark(PH_S_TGT);
-    AFS_PM(";MARK noise");
+    AFS_SCHED_BARRIER();
     if (U.opt.generate_noise_sources) {
       phase_noise<W, NZ>(x, X, U, C);
     } else {
@@ -2635,68 +2465,33 @@ AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Cons
         for (int d = gl; d < NDIP; d += W) X[X_SMP + d] = 0.0;
       });
     }
-#if AFS_PAIR_RNG_DYN
-    x.par([&](int gl, Lane<W> &R) {
-      if (gl == 0) {
-        int32_t *hp = (int32_t *)(X + X_RNGHP);
-        hp[0] = R.rhead;
-        hp[1] = R.rpend;
-      }
-    });
-#endif
-#endif
+    rng_ring_pos_store<W>(x, X);
     x.mark(PH_NOISE);
   }
   x.bar();
   x.mark(PH_P1WAIT);
-  if constexpr (ROLE == ROLE_STAT) {
-    if (pair_prio(x) == 2) AFS_SETPRIO(0);
-  }
-  AFS_PM(";MARK rows");
+  if (STAT && x.prio == 2) AFS_SETPRIO(0);
+  AFS_SCHED_BARRIER();
   x.par([&](int gl, Lane<W> &R) { phase_rows<W, ROLE>(gl, R, X, X, U, C); });
   x.mark(PH_ROWS);
   x.bar();
   x.mark(PH_P2WAIT);
-  AFS_PM(";MARK solver");
-  if constexpr (ROLE == ROLE_STAT) {
-    if (pair_prio(x) == 1 || pair_prio(x) == 2) AFS_SETPRIO(2);
-  }
-  if constexpr (ROLE == ROLE_STAT) {
-#if !defined(AFS_PAIR_PROBE_NOSOLVE)
-    // (64 lanes at one wave per SIMD: registers to spare for the full form)
-    solve_arms<W, Xc, AFS_PAIR_LEAN != 0 && (W != 64 || AFS_PAIR64_WAVES >= 2)>(x, X, C);
-#endif
-    AFS_PM(";MARK rng");
-#if !defined(AFS_PAIR_PROBE_NORNG) && !AFS_PAIR_RNG_DYN
+  AFS_SCHED_BARRIER();
+  if constexpr (STAT) {
+    if (x.prio == 1 || x.prio == 2) AFS_SETPRIO(2);
+    solve_arms<W, Xc, true>(x, X, C);
+    AFS_SCHED_BARRIER();
+  } else {
+    rng_ring_pos_load<W>(x, X);
     rng_ahead<W>(x, X);
-#endif
-  }
-#if AFS_PAIR_RNG_DYN
-  if constexpr (ROLE == ROLE_DYN) {  // the rand() blocks ahead on the DYN wave, beside the solver
-    x.par([&](int gl, Lane<W> &R) {
-      (void)gl;
-      const int32_t *hp = (const int32_t *)(X + X_RNGHP);
-      R.rhead = hp[0];
-      R.rpend = hp[1];
-    });
-    rng_ahead<W>(x, X);
-    x.par([&](int gl, Lane<W> &R) {
-      if (gl == 0) {
-        int32_t *hp = (int32_t *)(X + X_RNGHP);
-        hp[0] = R.rhead;
-        hp[1] = R.rpend;
-      }
-    });
+    rng_ring_pos_store<W>(x, X);
     x.mark(PH_RNGP);
   }
-#endif
   x.bar();
   x.mark(PH_P3WAIT);
-  if constexpr (ROLE == ROLE_STAT) {
-    if (pair_prio(x) == 1 || pair_prio(x) == 2) AFS_SETPRIO(0);
-  }
-  AFS_PM(";MARK update");
-  if constexpr (ROLE == ROLE_DYN)
+  if (STAT && (x.prio == 1 || x.prio == 2)) AFS_SETPRIO(0);
+  AFS_SCHED_BARRIER();
+  if constexpr (!STAT)
     x.par_uniform([&](int gl, Lane<W> &R) { phase_update<W, ROLE>(gl, R, X, X, U, C); },
                   [&](Lane<W> &R) { R.sample = phase_output_flow(X); });
   else
@@ -2710,7 +2505,6 @@ AFS_HD inline void sample_step_pair(Xc &x, double *X, const Uni &U, const Consts
   if (U.opt.glottis_loss == AFS_ENTRANCE_LOSS_VARIABLE) sample_step_pair_v<W, MODEL, NZ, ROLE, true>(x, X, U, C, ratio, par);
   else sample_step_pair_v<W, MODEL, NZ, ROLE, false>(x, X, U, C, ratio, par);
 }
-#endif
 
 }  // namespace tree
 }  // namespace afs

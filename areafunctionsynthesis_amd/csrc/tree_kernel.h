@@ -5,11 +5,14 @@
 // Mapping on gfx950: a wave64 holds four utterances, TREE_W = 16 lanes each.  A lane keeps
 // the state of its 6 sections (3 dynamic + 3 static) and their in-currents in registers
 // for the whole launch; the four utterances' 8.4 KB LDS blocks carry neighbour exchange,
-// the per-sample solver arrays and the small persistent state.  Waves never wait for one
-// another (no __syncthreads in the time loop): phases of one utterance are ordered by
-// wave-level fences, which is all LDS needs inside a wave.  The time loop runs inside the
-// kernel; a launch covers a range of frame transitions and saves the lane/LDS state at the
-// end, so long utterances and incremental sessions continue exactly where they stopped.
+// the per-sample solver arrays and the small persistent state.  In the one-wave kernel
+// (tree_synth_run) waves never wait for one another: phases of one utterance are ordered by
+// wave-level fences, which is all LDS needs inside a wave.  The default build's throughput kernel
+// and the voice kernel at small batches split each utterance's phases between two waves
+// (tree_pair_run), which meet at workgroup barriers (__syncthreads) in the time loop: four per
+// sample and one per frame transition.  The time loop runs inside the kernel; a launch covers a
+// range of frame transitions and saves the lane/LDS state at the end, so long utterances and
+// incremental sessions continue exactly where they stopped.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,13 +46,9 @@ constexpr int WPB = Geom<TW>::WPB;
 constexpr int UPB = Geom<TW>::UPB;
 static_assert(UPB == TREE_UPB, "afs_tree.h TREE_UPB: the host's slot orders group utterances by block");
 
-#ifndef AFS_PAIR_MARK_SB
-// the pair kernel: a scheduling barrier at the phase marks whose bit (tree_core.h PH_*) is set (A/B)
-#define AFS_PAIR_MARK_SB 0xFFFFFFFFu
-#endif
 template <bool PROF, int W = TW, bool MARK_SB = false>
 struct GpuExec {
-  static constexpr bool kToneOut = AFS_TONE_K6 != 0;  // the tone filter in K6 from the stored p[25] (afs_tree.h)
+  static constexpr bool kToneOut = true;        // the tone filter in K6 from the stored p[25] (afs_tree.h)
   static constexpr bool kGlottisSplit = true;   // the glottis' masses on the two lane halves (+1.1 %, r03ag_ab.txt)
   int gl;
   Lane<W> *R;
@@ -71,7 +70,7 @@ struct GpuExec {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  // the wave pairs' barrier (AFS_PAIR): every wave of the workgroup, LDS visible across them
+  // the wave pairs' barrier: every wave of the workgroup, LDS visible across them
   // (scheduling barriers around it: the scheduler does not mix the phases' code, which would keep
   // both phases' values live at once -- the pair kernel must fit 256 registers)
   __device__ __forceinline__ void bar() {
@@ -193,14 +192,15 @@ struct GpuExec {
     return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
   }
   // (MARK_SB, the wave pairs: a scheduling barrier at each phase mark -- the scheduler otherwise
-  // hoists a phase's loads into the one before and the pair kernel spills)
+  // hoists a phase's loads into the one before and the pair kernel spills: 270 -> 97 registers
+  // spilled, +8.7 %; without the barriers at the solver's marks alone -7.5 %, profiles/AB_LOG.md round 6)
   __device__ __forceinline__ void mark(int ph) {
     if constexpr (PROF) {
       uint64_t t = __builtin_amdgcn_s_memtime();
       acc[ph] += t - last;
       last = t;
     } else if constexpr (MARK_SB) {
-      if ((((uint32_t)AFS_PAIR_MARK_SB) >> ph) & 1u) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 };
@@ -213,6 +213,21 @@ struct WaveLdsT {
   double X[Geom<W>::UPB][X_STRIDE];
 };
 using WaveLds = WaveLdsT<TW>;
+
+// Whether this block has anything to do: not a launch of the hop-mode fast path whose mixed hops
+// overflowed K5's compact slots (the host runs the call through the chunked path instead,
+// afs_capi.cpp run_chunks), and not a block of padding slots only (the XCD-dealt slot order).
+template <int W>
+__device__ __forceinline__ bool block_has_work(const TreeArgs &a) {
+  if (a.skip_claims && (int64_t)*a.skip_claims > a.skip_cap) return false;
+  if (a.order) {
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < Geom<W>::UPB; ++g) any |= a.order[blockIdx.x * Geom<W>::UPB + g] < a.B;
+    if (!any) return false;
+  }
+  return true;
+}
 
 // The noise-phase variant a wave runs a launch in (tree_core.h NoiseV): the lightest one that
 // serves every dipole and constriction any sample of the launch may target -- the or of its
@@ -243,53 +258,11 @@ __device__ __forceinline__ int noise_variant(const TreeArgs &a, int g = -1, int 
 #pragma unroll
   for (int o = 32; o >= 1; o /= 2) m |= __shfl_xor(m, o, 64);
   int nz = NZ_FULL;
-  if ((AFS_NZ_SET & 4) && (m & ~NoiseV<W, NZ_T1ALL>::SERVES) == 0) nz = NZ_T1ALL;
-  if ((AFS_NZ_SET & 1) && (m & ~NoiseV<W, NZ_TONGUE1>::SERVES) == 0) nz = NZ_TONGUE1;
-  if ((AFS_NZ_SET & 2) && (m & ~NoiseV<W, NZ_GLOTTIS>::SERVES) == 0) nz = NZ_GLOTTIS;
+  if (nz_compiled(NZ_T1ALL) && (m & ~NoiseV<W, NZ_T1ALL>::SERVES) == 0) nz = NZ_T1ALL;
+  if (nz_compiled(NZ_TONGUE1) && (m & ~NoiseV<W, NZ_TONGUE1>::SERVES) == 0) nz = NZ_TONGUE1;
+  if (nz_compiled(NZ_GLOTTIS) && (m & ~NoiseV<W, NZ_GLOTTIS>::SERVES) == 0) nz = NZ_GLOTTIS;
   const int on = a.variants_dev ? *a.variants_dev : a.noise_variants;
   return __builtin_amdgcn_readfirstlane(on ? nz : (int)NZ_FULL);
-}
-
-// AFS_TONE_K6 == 2: the glottal-tone filter (TdsModel.cpp:494-510, 687-705) over positions j0 .. j1
-// of a 16-sample output window -- lane p of the utterance's row holds sample p's section-25 pressure
-// (wp) and radiated flow (wo) -- in sample order, with K6's operations in K6's order (uncontracted),
-// so the audio is the same bit for bit as with the filter in K6; the state (X_TONE) in LDS between
-// windows.  Every lane evaluates the recurrence (lane-uniform), lane p keeps its sample's sum.
-template <int P, class F> __device__ __forceinline__ void unroll16(F &f) {
-  f(std::integral_constant<int, P>{});
-  if constexpr (P + 1 < 16) unroll16<P + 1>(f);
-}
-template <class Ex>
-__device__ __forceinline__ void tone_window(int gl, double *X, const Consts &C, int j0, int j1, double &wo,
-                                            double wp) {
-#pragma clang fp contract(off)
-  double x1 = X[X_TONE + 0], x2 = X[X_TONE + 1], x3 = X[X_TONE + 2], x4 = X[X_TONE + 3];
-  double y1 = X[X_TONE + 4], y2 = X[X_TONE + 5], y3 = X[X_TONE + 6], y4 = X[X_TONE + 7];
-  const double *ta = C.h.tone_a, *tb = C.h.tone_b;
-  const double a0 = ta[0], a1 = ta[1], a2 = ta[2], a3 = ta[3], a4 = ta[4];
-  const double b1 = tb[1], b2 = tb[2], b3 = tb[3], b4 = tb[4];
-  auto step = [&](auto P) {
-    constexpr int p = decltype(P)::value;
-    if (p < j0 || p > j1) return;
-    const double xp = Ex::template dpp<0x150 + p>(wp);  // (row_newbcast p)
-    double tacc = a0 * xp;
-    tacc += a1 * x1;
-    tacc += b1 * y1;
-    tacc += a2 * x2;
-    tacc += b2 * y2;
-    tacc += a3 * x3;
-    tacc += b3 * y3;
-    tacc += a4 * x4;
-    tacc += b4 * y4;
-    x4 = x3; x3 = x2; x2 = x1; x1 = xp;
-    y4 = y3; y3 = y2; y2 = y1; y1 = tacc;
-    wo = gl == p ? wo + tacc : wo;
-  };
-  unroll16<0>(step);
-  if (gl == 0) {
-    X[X_TONE + 0] = x1; X[X_TONE + 1] = x2; X[X_TONE + 2] = x3; X[X_TONE + 3] = x4;
-    X[X_TONE + 4] = y1; X[X_TONE + 5] = y2; X[X_TONE + 6] = y3; X[X_TONE + 7] = y4;
-  }
 }
 
 // prof (PROF only): per wave, PH_COUNT cycle sums (s_memtime) over the launch.
@@ -297,8 +270,7 @@ __device__ __forceinline__ void tone_window(int gl, double *X, const Consts &C, 
 // gl's kind and inputs for the hop and evaluates the word at every sample; a mixed hop's samples
 // read their dense records as without HOPS.
 template <bool PROF, int MODEL, bool HOPS, int W, int NZ>
-__device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof,
-                                               int nz = NZ_FULL) {
+__device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
   constexpr int UPB_ = Geom<W>::UPB, WPB_ = Geom<W>::WPB;
   const int lane = threadIdx.x;  // 0 .. 64 WPB - 1
   const int g = lane / W, gl = lane % W;
@@ -385,26 +357,17 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
       next = pl[tn * PLAN_WORDS];  // the next sample's word, a sample ahead
       if (i + 1 == hop && t + 1 < n) nf.load(gl, fu + k + 1);
     }
-    sample_step<W, MODEL, NZ>(ex, X, a.uni, C, ratio, true, nz);
+    sample_step<W, MODEL, NZ>(ex, X, a.uni, C, ratio, true);
     {
       const int j = (o_line + (int)t) & 15;  // the sample's position in its line
       const double p25v = GpuExec<PROF, W>::template dpp<0x152>(R.p[0]);  // lane 2's p[25] to its row
       const bool mine = gl == j;
       wo = mine ? R.sample : wo;
       wp = mine ? p25v : wp;
-      if constexpr (AFS_TONE_K6 == 2) {
-        // the glottal-tone filter over the window's samples once it is complete (positions j0 .. j),
-        // its outputs added to the window's flows before the store (wave-uniform when the utterances'
-        // rows are congruent modulo 16 doubles, else per utterance)
-        if (j == 15 || t + 1 == n) {
-          const int j0 = t >= j ? 0 : (int)(j - t);
-          if (a.uni.opt.radiation_from_skin) tone_window<GpuExec<PROF, W>>(gl, X, C, j0, j, wo, wp);
-        }
-      }
       // lane gl stores window entry gl, sample t - j + gl, if it belongs to this launch
       if (valid && (j == 15 || t + 1 == n) && gl <= j && t - j + gl >= 0) {
         o[t - j + gl] = wo;
-        if constexpr (AFS_TONE_K6 == 1) p25o[t - j + gl] = wp;
+        p25o[t - j + gl] = wp;
       }
     }
     if (++i == hop) {
@@ -446,55 +409,30 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
 
 // The kernel body: in hop mode each wave picks its noise-phase variant for the launch
 // (noise_variant) and runs the whole body compiled for it.  (The waves of a block may take
-// different variants: each reaches the one __syncthreads of the table staging in its own copy.)
-#ifndef AFS_NZ_INNER
-#define AFS_NZ_INNER 0  // 1: one body, the variant switched in the noise phase (NZ_DYN); 0: a body per variant
-#endif
+// different variants: each reaches the one __syncthreads of the table staging in its own copy.  One
+// body with the variant switched in the noise phase instead -- sample_step's NZ_DYN -- measured
+// -1.7 %, profiles/r05f_variant_order_ab.txt.)
 template <bool PROF, int MODEL, bool HOPS = false, int W = TW>
 __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
-  // (a launch of the hop-mode fast path whose mixed hops overflowed K5's compact slots: the host runs
-  // the call through the chunked path instead, afs_capi.cpp run_chunks)
-  if (a.skip_claims && (int64_t)*a.skip_claims > a.skip_cap) return;
-  if (a.order) {  // a block of padding slots only (the XCD-dealt slot order) has nothing to do
-    bool any = false;
-#pragma unroll
-    for (int g = 0; g < Geom<W>::UPB; ++g) any |= a.order[blockIdx.x * Geom<W>::UPB + g] < a.B;
-    if (!any) return;
-  }
-  if constexpr (HOPS && AFS_NZ_INNER) {
-    tree_synth_run<PROF, MODEL, HOPS, W, NZ_DYN>(a, lds, prof, noise_variant<W>(a));
-  } else if constexpr (HOPS) {
-    const int nz = noise_variant<W>(a);
-    if (false) {
-#if AFS_NZ_SET & 2
-    } else if (nz == NZ_GLOTTIS) {
-      tree_synth_run<PROF, MODEL, HOPS, W, NZ_GLOTTIS>(a, lds, prof);
-#endif
-#if AFS_NZ_SET & 1
-    } else if (nz == NZ_TONGUE1) {
-      tree_synth_run<PROF, MODEL, HOPS, W, NZ_TONGUE1>(a, lds, prof);
-#endif
-#if AFS_NZ_SET & 4
-    } else if (nz == NZ_T1ALL) {
-      tree_synth_run<PROF, MODEL, HOPS, W, NZ_T1ALL>(a, lds, prof);
-#endif
-    } else {
-      tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL>(a, lds, prof);
-    }
+  if (!block_has_work<W>(a)) return;
+  if constexpr (HOPS) {
+    with_noise_variant(noise_variant<W>(a), [&](auto V) {
+      tree_synth_run<PROF, MODEL, HOPS, W, decltype(V)::value>(a, lds, prof);
+    });
   } else {
     tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL>(a, lds, prof);
   }
 }
 
 // ---------------------------------------------------------------------------
-// Wave pairs (AFS_PAIR = 1, an A/B build): a workgroup of four waves for the same eight utterances
-// -- waves 0 and 1 take the dynamic slots of utterances 0-3 / 4-7 (ROLE_DYN), waves 2 and 3 their
+// Wave pairs (the default build's throughput kernel, afs_tree.h AFS_PAIR): a workgroup of four
+// waves for the same eight utterances -- two take the dynamic slots of utterances 0-3 / 4-7
+// (ROLE_DYN), two their
 // static slots and the lane-uniform phases (ROLE_STAT) -- and two workgroups per CU: two waves per
 // SIMD, whose instructions the SIMD interleaves (a wave alone issues one VALU instruction per 4
 // cycles; the SIMD executes one per 2, tree_core.h sample_step_pair).  Each wave holds half the
 // slots' state, so the pair's kernel must fit 256 registers per lane.
 // ---------------------------------------------------------------------------
-#if AFS_PAIR
 // (W = 64: the voice kernel's pairs, one utterance per workgroup of two waves, tree_pair64_body)
 template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW>
 __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &lds, int grp, uint64_t *prof = nullptr) {
@@ -520,7 +458,7 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
     for (int k = gl; k < X_TOTAL; k += W) X[k] = ls[k];
   __syncthreads();
   const Consts &C = lds.C;
-  GpuExec<PROF, W, AFS_PAIR_MARK_SB != 0> ex{gl, &R};
+  GpuExec<PROF, W, true> ex{gl, &R};
   ex.prio = a.stat_prio;
   const int64_t row = a.frame_row ? a.frame_row[ue] : ue;
   const afs_frame *fu = a.frames + row * a.frame_stride;
@@ -549,7 +487,6 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
   const int o_line = (int)((reinterpret_cast<uintptr_t>(o) >> 3) & 15);
   double wo = 0.0, wp = 0.0;
   const double dhop = (double)hop, inv_hop = 1.0 / dhop;
-#if AFS_PAIR_RNG_DYN
   if constexpr (ROLE == ROLE_STAT) {  // (the ring's head and pending count from the saved lane state)
     if (gl == 0) {
       int32_t *hp = (int32_t *)(X + X_RNGHP);
@@ -557,12 +494,11 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
       hp[1] = R.rpend;
     }
   }
-#endif
   __syncthreads();  // (the LDS image and X_FRAME in place for both roles)
   uint64_t next = 0;
   if constexpr (ROLE == ROLE_STAT) next = hmixed ? (HOPS ? pd[i * PLAN_WORDS] : pl[0]) : 0;
   if constexpr (ROLE == ROLE_STAT) {
-    if (pair_prio(ex) == 3) AFS_SETPRIO(2);  // (the whole launch; modes 1, 2: sample_step_pair)
+    if (ex.prio == 3) AFS_SETPRIO(2);  // (the whole launch; modes 1, 2: sample_step_pair)
   }
   uint64_t t_begin = 0;
   if constexpr (PROF) t_begin = ex.last = __builtin_amdgcn_s_memtime();
@@ -590,7 +526,7 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
       wp = mine ? p25v : wp;
       if (valid && (j == 15 || t + 1 == n) && gl <= j && t - j + gl >= 0) {
         o[t - j + gl] = wo;
-        if constexpr (AFS_TONE_K6 == 1) p25o[t - j + gl] = wp;
+        p25o[t - j + gl] = wp;
       }
     }
     if (++i == hop) {
@@ -650,52 +586,32 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
       for (int q = 0; q < S::NDP; ++q) {
         dst->damp[q] = R.damp[q]; dst->dout[q] = R.dout[q]; dst->dcut[q] = R.dcut[q]; dst->racc[q] = R.racc[q];
       }
-#if AFS_PAIR_RNG_DYN
       const int32_t *hp = (const int32_t *)(X + X_RNGHP);
       dst->rhead = hp[0];
       dst->rpend = hp[1];
-#else
-      dst->rhead = R.rhead;
-      dst->rpend = R.rpend;
-#endif
     }
   }
 }
 
-// The two workgroups a compute unit holds at a time (AFS_PAIR_MAP 3): each claims one of two slots
+// The two workgroups a compute unit holds at a time: each claims one of two slots
 // in its CU's word (global atomics; released when the workgroup ends).
 __device__ unsigned int pair_cu_slots[2048];
 
 // Roles: two groups of four utterances; in each group one wave is DYN and one STAT.  The SIMD a wave
-// runs on decides (AFS_PAIR_MAP 3), so that each SIMD runs one DYN and one STAT wave of its CU's two
+// runs on decides, so that each SIMD runs one DYN and one STAT wave of its CU's two
 // workgroups -- STAT carries the targets, noise and solver, the longer half: two STAT waves on one
-// SIMD would share its issue slots.  When a workgroup's four waves do not sit on four SIMDs, or
-// under the other maps, by the wave index (0: waves 0, 1 DYN; 1: a slot parity read from
-// HW_ID.WAVE_ID; 2: the block's parity).  Any placement gives a valid pairing; this only balances
-// the SIMDs.
+// SIMD would share its issue slots.  When a workgroup's four waves do not sit on four SIMDs, by the
+// wave index.  Any placement gives a valid pairing; this only balances the SIMDs (against roles by
+// the wave index, the wave slot's or the block's parity: profiles/r06_pair_ab.txt).
 template <int MODEL, bool HOPS, bool PROF = false>
 __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &lds, int *pattern,
                                                uint64_t *prof = nullptr) {
-  if (a.skip_claims && (int64_t)*a.skip_claims > a.skip_cap) return;
-  if (a.order) {
-    bool any = false;
-#pragma unroll
-    for (int g = 0; g < Geom<TW>::UPB; ++g) any |= a.order[blockIdx.x * Geom<TW>::UPB + g] < a.B;
-    if (!any) return;
-  }
+  if (!block_has_work<TW>(a)) return;
   const int wave = (int)threadIdx.x / 64;
-#ifndef AFS_PAIR_MAP
-// 3: by SIMD and the CU's workgroup slot; 0: waves 0, 1 DYN (groups 0, 1), 2, 3 STAT; 1: by the wave
-// slot's parity; 2: by the block's parity (profiles/r06_pair_ab.txt)
-#define AFS_PAIR_MAP 3
-#endif
   int grp, st;
   unsigned int *cu_word = nullptr;
   unsigned int cu_bit = 0;
-  if constexpr (AFS_PAIR_MAP == 0) {
-    grp = wave & 1;
-    st = wave >> 1;
-  } else if constexpr (AFS_PAIR_MAP == 3) {
+  {
     const unsigned int hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID
     const int simd = (int)((hw >> 4) & 3);
     if (threadIdx.x % 64 == 0) pattern[1 + wave] = simd;
@@ -719,42 +635,19 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
       grp = wave & 1;
       st = (wave >> 1) ^ pattern[0];
     }
-  } else {
-    if (threadIdx.x == 0)
-      *pattern = AFS_PAIR_MAP == 1 ? (int)(__builtin_amdgcn_s_getreg((3 << 11) | 4) & 1)  // HW_ID.WAVE_ID bit 0
-                                   : (int)(blockIdx.x & 1);
-    __syncthreads();
-    grp = wave >> 1;
-    st = (wave & 1) ^ *pattern;
   }
   const bool stat = st != 0;
-#ifdef AFS_PAIR_PROBE  // (register probes: 1 compiles the DYN role alone, 2 the STAT role's NZ_FULL copy alone)
-  if constexpr (AFS_PAIR_PROBE == 1) { tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF>(a, lds, grp, prof); return; }
-  if constexpr (AFS_PAIR_PROBE == 2) { tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF>(a, lds, grp, prof); return; }
-#endif
   if (!stat) {
     tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF>(a, lds, grp, prof);
   } else if constexpr (HOPS) {
     const int g = grp * Geom<TW>::UPW + ((int)threadIdx.x % 64) / TW, gl = (int)threadIdx.x % TW;
-    const int nz = noise_variant<TW>(a, g, gl);
-    if (false) {
-#if AFS_NZ_SET & 2
-    } else if (nz == NZ_GLOTTIS) {
-      tree_pair_run<MODEL, HOPS, NZ_GLOTTIS, ROLE_STAT, PROF>(a, lds, grp, prof);
-#endif
-#if AFS_NZ_SET & 1
-    } else if (nz == NZ_TONGUE1) {
-      tree_pair_run<MODEL, HOPS, NZ_TONGUE1, ROLE_STAT, PROF>(a, lds, grp, prof);
-#endif
-    } else {
-      tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF>(a, lds, grp, prof);
-    }
+    with_noise_variant(noise_variant<TW>(a, g, gl), [&](auto V) {
+      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF>(a, lds, grp, prof);
+    });
   } else {
     tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF>(a, lds, grp, prof);
   }
-  if constexpr (AFS_PAIR_MAP == 3) {
-    if (threadIdx.x == 0 && cu_bit) atomicAnd(cu_word, ~cu_bit);  // (after the run's last workgroup barrier)
-  }
+  if (threadIdx.x == 0 && cu_bit) atomicAnd(cu_word, ~cu_bit);  // (after the run's last workgroup barrier)
 }
 
 // The voice kernel's pairs (64 lanes per utterance): one utterance per workgroup of two waves, wave 0
@@ -762,31 +655,18 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
 // sample's chain split over two SIMDs instead of one wave's.
 template <int MODEL, bool HOPS, bool PROF = false>
 __device__ __forceinline__ void tree_pair64_body(const TreeArgs &a, WaveLdsT<64> &lds, uint64_t *prof = nullptr) {
-  if (a.skip_claims && (int64_t)*a.skip_claims > a.skip_cap) return;
-  if (a.order && a.order[blockIdx.x] >= a.B) return;
+  if (!block_has_work<64>(a)) return;
   const bool stat = threadIdx.x >= 64;
   if (!stat) {
     tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, 64>(a, lds, 0, prof);
   } else if constexpr (HOPS) {
-    const int nz = noise_variant<64>(a, 0, (int)threadIdx.x % 64);
-    if (false) {
-#if AFS_NZ_SET & 2
-    } else if (nz == NZ_GLOTTIS) {
-      tree_pair_run<MODEL, HOPS, NZ_GLOTTIS, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
-#endif
-#if AFS_NZ_SET & 1
-    } else if (nz == NZ_TONGUE1) {
-      tree_pair_run<MODEL, HOPS, NZ_TONGUE1, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
-#endif
-    } else {
-      tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
-    }
+    with_noise_variant(noise_variant<64>(a, 0, (int)threadIdx.x % 64), [&](auto V) {
+      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
+    });
   } else {
     tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
   }
 }
-
-#endif  // AFS_PAIR
 
 }  // namespace tree
 }  // namespace afs

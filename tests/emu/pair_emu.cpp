@@ -1,5 +1,5 @@
-// pair_emu.cpp -- TEST-ONLY host execution of the wave-pair step (tree_core.h sample_step_pair,
-// compiled with AFS_PAIR=1): the DYN and the STAT role of one utterance run on two threads that meet
+// pair_emu.cpp -- TEST-ONLY host execution of the wave-pair step (tree_core.h sample_step_pair):
+// the DYN and the STAT role of one utterance run on two threads that meet
 // at the step's workgroup barriers (x.bar()), each over its own lane array, both on one LDS block --
 // the decomposition tree_kernel.h tree_pair_run runs on two waves.  tests/test_tree_emu.py checks it
 // against the one-wave step (tree_emu.cpp, tone filter in K6 as on the device) bit for bit.  Never
@@ -13,8 +13,6 @@ using namespace afs;
 using namespace afs::tree;
 
 #include "cpu_exec.h"
-
-static_assert(AFS_PAIR, "build with -DAFS_PAIR=1");
 
 namespace {
 

@@ -288,7 +288,7 @@ def test_noise_variants_bitwise(emu, oracle, hop_mode, W):
 
 @pytest.mark.parametrize("case", ["tiny_pharynx", "alternating", "wide_open"])
 def test_arm_scan_extreme_areas_vs_oracle(emu, oracle, case):
-    """The arm solver's lane scans (tree_core.h solve_arms, AFS_ARM_SCAN) on tracts far outside
+    """The arm solver's lane scans (tree_core.h solve_arms) on tracts far outside
     speech: sections at the area clamp beside 60 cm^2 sections, a whole pharynx at the clamp, every
     section wide open.  The pivot recurrence's 2 x 2 products span up to 8 lanes, an arm's first lane
     included (its F = 0 makes the ratio, not the magnitude, independent of the lanes before it): the

@@ -18,7 +18,7 @@ using namespace afs::tree;
 constexpr int PW = PP_W;
 // (HOPS: K5's hop records and the noise-phase variants, as the library's large calls run)
 #if AFS_PAIR && PP_W == AFS_TREE_W
-// the wave-pair kernel (AFS_PAIR=1 builds, 16 lanes per utterance): four waves per block
+// the wave-pair kernel (the default build, 16 lanes per utterance): four waves per block
 constexpr int PWPB = 4, PUPB = Geom<PW>::UPB;
 template <bool HOPS>
 __global__ void __launch_bounds__(256, 2) tree_prof_kernel(TreeArgs a, uint64_t *prof) {
@@ -27,10 +27,10 @@ __global__ void __launch_bounds__(256, 2) tree_prof_kernel(TreeArgs a, uint64_t 
   tree_pair_body<AFS_GLOTTIS_TRIANGULAR, HOPS, true>(a, lds, pattern, prof);
 }
 #elif AFS_PAIR && PP_W == 64
-// the voice kernel's pairs (AFS_PAIR builds, -DPP_W=64): two waves per utterance
+// the voice kernel's pairs (the default build, -DPP_W=64): two waves per utterance
 constexpr int PWPB = 2, PUPB = 1;
 template <bool HOPS>
-__global__ void __launch_bounds__(128, AFS_PAIR64_WAVES) tree_prof_kernel(TreeArgs a, uint64_t *prof) {
+__global__ void __launch_bounds__(128, 2) tree_prof_kernel(TreeArgs a, uint64_t *prof) {
   __shared__ WaveLdsT<64> lds;
   tree_pair64_body<AFS_GLOTTIS_TRIANGULAR, HOPS, true>(a, lds, prof);
 }

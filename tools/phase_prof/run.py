@@ -17,8 +17,8 @@ sys.path.insert(0, os.path.join(HERE, "..", ".."))
 PHASES = ["geometry", "network", "n:filter", "n:act", "n:rng", "rows", "forward", "backward", "update",
           "output", "targets", "pair:P1 wait", "pair:P2 wait", "pair:P3 wait", "pair:P4 wait", "pair:rng (DYN)",
           "pair:tail", "pair:glottis+static net (STAT)", "pair:targets (STAT)", "pair:interp+glottis (DYN)",
-          "pair:P0 wait", "(placement)", "(t0)", "(t1)"]
-PLACE = 21  # tree_core.h PH_PLACE_HW, then the loop's first and last memtime
+          "(placement)", "(t0)", "(t1)"]
+PLACE = 20  # tree_core.h PH_PLACE_HW, then the loop's first and last memtime
 
 
 def main():
