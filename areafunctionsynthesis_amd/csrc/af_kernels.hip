@@ -157,11 +157,13 @@ __global__ void target_frames_kernel(const double *seq, int Q, TargetPlan t, int
 // phases first, so that a wave's four utterances share one variant), then where (section index),
 // then the area itself (a float's bits: positive floats order as their bits).  Ascending, the
 // narrowest constrictions -- the utterances with turbulence noise, the heaviest -- come first and
-// alike shapes sit together.  (Measured against the section-major key: +0.8 % static vowels, equal
-// on fricatives; descending: -1.3 %; profiles/r04v_shape_key_ab.txt.  The class as the first key
+// alike shapes sit together.  Bits: the bucket from 48, the class at KEY_CLASS_SHIFT, the section from
+// 32, the area below.  (Measured against the section-major key: +0.8 % static vowels, equal on
+// fricatives; descending: -1.3 %; profiles/r04v_shape_key_ab.txt.  The class as the first key
 // instead of the second: within 0.2 %, profiles/r05g_class_key_ab.txt; no class key with the
 // variants: -5 %, r05c_variants_ab.txt.)  A NaN area counts as wide.
-__global__ void utterance_key_kernel(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys, int noise_class) {
+constexpr int KEY_CLASS_SHIFT = 40;
+__global__ void utterance_key_kernel(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= B) return;
   const afs_frame *f = frames + (int64_t)u * fstride;
@@ -176,31 +178,30 @@ __global__ void utterance_key_kernel(const afs_frame *frames, int64_t fstride, i
   tree::PlanKey k;
   double obst[4], po[4];
   plan_decide(tree::PlanGeomT<false>{f, f, 1.0, 0.0}, k, obst, po);  // (the first frame's decisions)
-  const uint64_t cls = noise_class ? (uint64_t)tree::plan_noise_class16(tree::plan_key_noise(k), AFS_NZ_SET) : 0;
-  keys[u] = noise_class == 2  // (the class after the narrowness bucket)
-                ? ((uint64_t)bucket << 48) | (cls << 40) | ((uint64_t)imin << 32) | (uint64_t)__float_as_uint(af)
-                : (cls << 48) | ((uint64_t)bucket << 40) | ((uint64_t)imin << 32) | (uint64_t)__float_as_uint(af);
+  const uint64_t cls = (uint64_t)tree::plan_noise_class16(tree::plan_key_noise(k), AFS_NZ_SET);
+  keys[u] = ((uint64_t)bucket << 48) | (cls << KEY_CLASS_SHIFT) | ((uint64_t)imin << 32) |
+            (uint64_t)__float_as_uint(af);
 }
 
 // The slot order's rule on the device (afs_capi.cpp shape_order, one block): whether the call runs
 // the noise-phase variants -- mode 2 always, 0 never, 1 when at least half the utterances have a light
-// noise class (the class field at bit `shift` non-zero) or every SIMD runs many waves -- into
+// noise class (the keys' class field non-zero) or every SIMD runs many waves -- into
 // *variants; without them the class field is masked out of the keys (it then plays no part in the
 // order); idx[u] = u; the padding slots order[B .. slots) = B.
-__global__ void __launch_bounds__(1024) order_rule_kernel(uint64_t *keys, int B, int shift, int mode, int many_waves,
+__global__ void __launch_bounds__(1024) order_rule_kernel(uint64_t *keys, int B, int mode, int many_waves,
                                                           int32_t *variants, int32_t *idx, int32_t *order, int slots) {
   __shared__ int light;
   if (threadIdx.x == 0) light = 0;
   __syncthreads();
-  if (mode == 1 && shift >= 0) {
+  if (mode == 1) {
     int n = 0;
-    for (int u = threadIdx.x; u < B; u += blockDim.x) n += ((keys[u] >> shift) & 3) != 0;
+    for (int u = threadIdx.x; u < B; u += blockDim.x) n += ((keys[u] >> KEY_CLASS_SHIFT) & 3) != 0;
     atomicAdd(&light, n);
   }
   __syncthreads();
   const bool on = mode == 2 || (mode == 1 && (2 * (int64_t)light >= (int64_t)B || many_waves != 0));
   if (threadIdx.x == 0) *variants = on ? 1 : 0;
-  const uint64_t mask = (shift >= 0 && !on) ? ~(3ull << shift) : ~0ull;
+  const uint64_t mask = on ? ~0ull : ~(3ull << KEY_CLASS_SHIFT);
   for (int u = threadIdx.x; u < B; u += blockDim.x) {
     keys[u] &= mask;
     idx[u] = u;
@@ -210,23 +211,22 @@ __global__ void __launch_bounds__(1024) order_rule_kernel(uint64_t *keys, int B,
 
 }  // namespace
 
-hipError_t launch_slot_order(uint64_t *keys, uint64_t *keys_sorted, int32_t *idx, int B, int shift, int mode,
-                             bool many_waves, int32_t *variants, int32_t *order, int slots, void *temp,
-                             size_t *temp_bytes, hipStream_t st) {
+hipError_t launch_slot_order(uint64_t *keys, uint64_t *keys_sorted, int32_t *idx, int B, int mode, bool many_waves,
+                             int32_t *variants, int32_t *order, int slots, void *temp, size_t *temp_bytes,
+                             hipStream_t st) {
   if (!temp) return hipcub::DeviceRadixSort::SortPairs(nullptr, *temp_bytes, keys, keys_sorted, idx, order, B, 0, 64, st);
-  hipLaunchKernelGGL(order_rule_kernel, dim3(1), dim3(1024), 0, st, keys, B, shift, mode, many_waves ? 1 : 0,
-                     variants, idx, order, slots);
+  hipLaunchKernelGGL(order_rule_kernel, dim3(1), dim3(1024), 0, st, keys, B, mode, many_waves ? 1 : 0, variants, idx,
+                     order, slots);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // stable (LSD radix): ties keep the utterance order, as the host's stable sort did
   return hipcub::DeviceRadixSort::SortPairs(temp, *temp_bytes, keys, keys_sorted, idx, order, B, 0, 64, st);
 }
 
-hipError_t launch_utterance_keys(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys, int noise_class,
-                                 hipStream_t st) {
+hipError_t launch_utterance_keys(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys, hipStream_t st) {
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(utterance_key_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, frames, fstride, B,
-                     keys, noise_class);
+                     keys);
   return hipGetLastError();
 }
 

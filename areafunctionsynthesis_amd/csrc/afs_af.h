@@ -30,18 +30,16 @@ hipError_t launch_target_frames(const double *seq, int Q, const TargetPlan &plan
                                 int64_t fstride, afs_frame *frames, hipStream_t st);
 
 // keys[u] = the shape key of utterance u's first frame frames[u * fstride] (how narrow its tube is
-// and where), for the slot order of the tree kernel (afs_capi.cpp shape_order).
-// (noise_class: 1 the noise class as the key's first field, 2 after the narrowness bucket, 0 not
-// in the key; af_kernels.hip)
-hipError_t launch_utterance_keys(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys, int noise_class,
-                                 hipStream_t st);
+// and where, its noise class after the narrowness bucket; af_kernels.hip), for the slot order of the
+// tree kernel (afs_capi.cpp shape_order).
+hipError_t launch_utterance_keys(const afs_frame *frames, int64_t fstride, int B, uint64_t *keys, hipStream_t st);
 
 // The slot order on the device from keys[B] (launch_utterance_keys; overwritten): the variant rule
-// (mode 0 never, 1 the rule, 2 always; the class field at bit `shift`, -1: none) into *variants, the
-// utterances sorted stably by their (masked) keys into order[0 .. B), order[B .. slots) = B.
+// (mode 0 never, 1 the rule, 2 always) into *variants, the utterances sorted stably by their keys
+// (without the variants: less the class field) into order[0 .. B), order[B .. slots) = B.
 // keys_sorted[B], idx[B]: scratch.  temp == nullptr: only *temp_bytes is set (the sort's scratch).
-hipError_t launch_slot_order(uint64_t *keys, uint64_t *keys_sorted, int32_t *idx, int B, int shift, int mode,
-                             bool many_waves, int32_t *variants, int32_t *order, int slots, void *temp,
-                             size_t *temp_bytes, hipStream_t st);
+hipError_t launch_slot_order(uint64_t *keys, uint64_t *keys_sorted, int32_t *idx, int B, int mode, bool many_waves,
+                             int32_t *variants, int32_t *order, int slots, void *temp, size_t *temp_bytes,
+                             hipStream_t st);
 
 }  // namespace afs

@@ -22,6 +22,7 @@
 #include "afs_ctx.h"
 #include "afs_model.h"
 #include "afs_tree.h"
+#include "afs_xcd_order.h"
 
 static_assert(sizeof(afs_frame) == 1072, "afs_frame layout");
 
@@ -65,6 +66,7 @@ afs_status ensure(afs_ctx *c, void **buf, size_t *cap, size_t bytes) {
   *cap = 0;
   HIP_TRY(c, hipMalloc(buf, bytes));
   *cap = bytes;
+  if (std::find(c->grown.begin(), c->grown.end(), buf) == c->grown.end()) c->grown.push_back(buf);
   return AFS_OK;
 }
 
@@ -95,15 +97,12 @@ bool tree(const afs_ctx *c) { return c->cfg.solver == AFS_SOLVER_TREE; }
 // profiles/r04h_launch_ab.txt.)
 constexpr int64_t PLAN_BUDGET_DEFAULT = (int64_t)4 << 30;
 // Hop mode: calls whose dense records fit this many bytes even with every hop listed skip the
-// read-back of K5's work-list length (run_chunks).
+// read-back of K5's claimed slots (run_hop_call).
 constexpr int64_t SMALL_CALL_DENSE_BYTES = (int64_t)64 << 20;
 
-// Launch the synthesis of frame transitions 1 .. ntrans (frames[row * fstride + k], k = 0 the
-// latched frame) in chunks that keep each kernel well below a second; state is carried
-// between launches.  rows: number of distinct frame rows (B, or the target sequences).
 // AFS_PROFILE: record an event on the context's stream (a pooled one; recording stops past
 // the pool's cap until afs_kernel_times drains it).
-hipEvent_t prof_event(afs_ctx *c, hipStream_t st) {
+hipEvent_t prof_event(afs_ctx *c) {
   if (!(c->cfg.flags & AFS_PROFILE)) return nullptr;
   constexpr size_t CAP = 1 << 14;
   if (c->pev_used == c->pev.size()) {
@@ -115,39 +114,11 @@ hipEvent_t prof_event(afs_ctx *c, hipStream_t st) {
     c->pev.push_back(e);
   }
   hipEvent_t e = c->pev[c->pev_used++];
-  if (hipEventRecord(e, st) != hipSuccess) return nullptr;
+  if (hipEventRecord(e, c->stream) != hipSuccess) return nullptr;
   return e;
 }
-hipEvent_t prof_event(afs_ctx *c) { return prof_event(c, c->stream); }
 void prof_pair(afs_ctx *c, hipEvent_t a, hipEvent_t b, int kind) {
   if (a && b) c->timed.push_back({a, b, kind});
-}
-
-// Slot order of the tree kernel for utterances that share trajectories (row[u]: the utterance's
-// frame row): the utterances sorted by row, and the sorted list cut into contiguous chunks so that
-// the blocks one XCD runs at the same time play as few rows as possible -- each of the 8 XCDs has
-// its own L2, and blocks are dealt to them round-robin (block b shares an XCD with b + 8,
-// MI355X_MICROARCH.md, workgroup dispatch), in rounds of `conc` blocks (the blocks the GPU holds
-// at once).  Entry (block * upb + g) = the utterance of that slot, B for padding slots.
-std::vector<int32_t> xcd_order(const std::vector<int32_t> &row, int B, int upb, int conc) {
-  constexpr int XCDS = 8;
-  std::vector<int32_t> idx((size_t)B);
-  for (int u = 0; u < B; ++u) idx[(size_t)u] = u;
-  std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return row[(size_t)a] < row[(size_t)b]; });
-  const int nb = (B + upb - 1) / upb;
-  conc = std::max(conc, 1);
-  std::vector<int32_t> order((size_t)nb * (size_t)upb, B);
-  for (int r0 = 0; r0 < nb; r0 += conc) {  // one round: blocks r0 .. r0 + nr - 1
-    const int nr = std::min(conc, nb - r0);
-    int chunk = r0;  // (the sorted chunks of this round, XCD by XCD)
-    for (int x = 0; x < XCDS; ++x)
-      for (int b = r0 + x; b < r0 + nr; b += XCDS, ++chunk)
-        for (int g = 0; g < upb; ++g) {
-          const int64_t q = (int64_t)chunk * upb + g;
-          if (q < B) order[(size_t)b * upb + g] = idx[(size_t)q];
-        }
-  }
-  return order;
 }
 
 // A call's slot order for K1 (shape_order): the order (null: the identity), the launch's blocks, and
@@ -165,194 +136,231 @@ SlotOrder plain_order(const afs_ctx *c) {
   return so;
 }
 
-afs_status run_chunks(afs_ctx *c, const afs_frame *frames, int64_t fstride, int rows, int ntrans, int hop,
-                      double *out, int64_t ostride, void *ws, int32_t *rng, void *lanes, int64_t bp, int B,
-                      int width, const int32_t *frame_row, const SlotOrder &so) {
-  if (tree(c)) {
-    const int64_t S = (int64_t)ntrans * hop;
-    const int two = c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0;
-    const afs::SecRec *uo = c->dev_tab->consts.sec;
-    afs_status st;
-    // K6's glottal-tone input: section 25's pressure per sample of a launch.  Laid out so that
-    // every utterance's row sits at the same position in its 128-byte lines as its output row
-    // (stride and base congruent to the output's modulo 16 doubles): K1 stores both through one
-    // line-aligned window (tree_kernel.h).
-    auto p25_for = [&](int64_t per, int64_t *stride) -> afs_status {
-      *stride = per + ((ostride - per) % 16 + 16) % 16;
-      return ensure(c, &c->p25, &c->p25_bytes, ((size_t)B * (size_t)*stride + 32) * sizeof(double));
-    };
-    auto p25_row0 = [&](int64_t s0) {  // the p25 base for the launch whose outputs start at out + s0
-      const int64_t want = (int64_t)((reinterpret_cast<uintptr_t>(out + s0) >> 3) & 15);
-      const int64_t have = (int64_t)((reinterpret_cast<uintptr_t>(c->p25) >> 3) & 15);
-      return (double *)c->p25 + ((want - have) % 16 + 16) % 16;
-    };
-    // K1 over samples [s0, s1), then K6 over them (both timed)
-    // (skip: the launches of the hop-mode fast path when its compact slots may overflow: they do
-    // nothing when K5 claimed more than skip_cap slots)
-    auto synth = [&](int64_t s0, int64_t s1, const uint64_t *plan, int64_t plan_stride, const afs::tree::PlanHop *hops,
-                     int64_t hop_stride, int64_t p25_stride, const uint32_t *skip = nullptr,
-                     int64_t skip_cap = 0) -> afs_status {
-      afs::TreeArgs a{c->dev_tab, frames, fstride, frame_row, hop, s0, s1, out + s0, ostride, plan, plan_stride, lanes,
-                      (double *)ws, B, c->host_tab.uni, hops, hop_stride, p25_row0(s0), p25_stride, so.order,
-                      so.variants ? 1 : 0, so.grid, so.variants_dev, skip, skip_cap};
-      {  // the pairs' STAT priority mode by the launch's rounds of workgroups per CU slot (two per CU)
-        const int64_t blocks = so.grid > 0 ? so.grid : ((int64_t)B + afs::TREE_UPB - 1) / afs::TREE_UPB;
-        const int64_t slots = std::max<int64_t>(1, c->simds / 2), rounds = (blocks + slots - 1) / slots;
-        a.stat_prio = c->stat_prio >= 0 ? c->stat_prio : ((width == afs::TREE_W && rounds >= 2) ? 2 : 0);
-      }
-      hipEvent_t e1 = prof_event(c);
-      HIP_TRY(c, afs::launch_tree_synth(a, width, c->stream));
-      hipEvent_t e2 = prof_event(c);
-      prof_pair(c, e1, e2, 0);
-      // K6: the glottal-tone filter and the output stage of the launch's samples
-      HIP_TRY(c, afs::launch_tree_output(c->dev_tab, (double *)ws, out + s0, ostride, s1 - s0, B,
-                                         p25_row0(s0), p25_stride,
-                                         c->cfg.options.radiation_from_skin, c->stream, skip, skip_cap));
-      prof_pair(c, e2, prof_event(c), 2);
-      return AFS_OK;
-    };
-    // Hop mode (tree solver, hops >= PLAN_HOP_MIN): K5 decides every hop of the call first -- one
-    // record per (row, hop), the hops it cannot decide at once listed -- and K5's second stage
-    // decides the listed hops sample by sample, writing the dense records of the mixed ones (whose
-    // samples differ) into a compact array (one hop-long slot each, claimed from a counter).  K1
-    // then runs the call in launches of up to 65536 samples, each hop's words evaluated from its
-    // record (or read from its dense slot).  One K1 launch per second of 44.1 kHz audio instead of
-    // one per 4096 samples: no state save / restore and launch tail in between (+0.6 %,
-    // profiles/r04c_store_launch_ab.txt).  A call whose mixed hops' records would exceed the plan
-    // budget falls back to the chunked path.
-    const bool hops = !c->plan_dense && hop >= afs::tree::PLAN_HOP_MIN;
-    const int64_t call_hops = afs::plan_hop_slots(0, S, hop);
-    if (hops && (int64_t)rows * call_hops * (int64_t)sizeof(afs::tree::PlanHop) <= c->plan_budget) {
-      const int64_t hstride = call_hops;
-      const size_t hbytes = (size_t)rows * (size_t)hstride * sizeof(afs::tree::PlanHop);
-      if ((st = ensure(c, &c->hops[0], &c->hops_bytes[0], hbytes)) != AFS_OK) return st;
-      if ((st = ensure(c, &c->plan_work[0], &c->plan_work_bytes[0], (size_t)afs::plan_work_bytes(rows, hstride))) != AFS_OK)
-        return st;
-      afs::tree::PlanHop *hbuf = (afs::tree::PlanHop *)c->hops[0];
-      uint32_t *work = (uint32_t *)c->plan_work[0];
-      afs::PlanArgs pa{c->dev_tab, frames, fstride, rows, hop, 0, S, nullptr, 0, two, uo, hbuf, hstride, work, true};
-      hipEvent_t e0 = prof_event(c);
-      HIP_TRY(c, afs::launch_plan_hops_iv(pa, c->stream));
-      // Slots for the mixed hops: one for every hop of the call when they fit the budget (small calls:
-      // real-time sessions, short batches), else the budget's worth.  No host read-back before K1: the
-      // launches are queued at once, guarded by the count of slots K5's second stage claimed (they do
-      // nothing if it exceeds the slots); the host then waits for K5 alone -- the launches are already
-      // queued behind it, so the device never idles for the host -- and, in the rare call whose mixed
-      // hops overflowed the slots, queues the chunked path below (most listed hops are not mixed:
-      // near-ties decided alike by every sample; static vowels have none).
-      const int64_t slot_bytes = (int64_t)hop * afs::PLAN_RECORD_BYTES;
-      const int64_t every = (int64_t)rows * call_hops;
-      const bool small = every * slot_bytes <= std::min<int64_t>(c->plan_budget, SMALL_CALL_DENSE_BYTES);
-      const int64_t cap = small ? every : std::min<int64_t>(every, std::max<int64_t>(1, c->plan_budget / slot_bytes));
-      if ((st = ensure(c, &c->plan, &c->plan_bytes, (size_t)(cap * slot_bytes))) != AFS_OK) return st;
-      pa.plan = (uint64_t *)c->plan;
-      pa.dense_cap = cap;
-      HIP_TRY(c, afs::launch_plan_hops_wave(pa, c->stream));
-      const bool guard = cap < every;
-      if (guard) {
-        HIP_TRY(c, hipMemcpyAsync(c->hcount, work + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_k5, c->stream));
-      }
-      prof_pair(c, e0, prof_event(c), 1);
-      const int64_t per = std::min<int64_t>(S, c->launch_cap);
-      int64_t p25_stride = 0;
-      if ((st = p25_for(per, &p25_stride)) != AFS_OK) return st;
-      for (int64_t s0 = 0; s0 < S; s0 += per) {
-        const int64_t s1 = std::min(S, s0 + per);
-        // (K1 indexes the records from the launch's first hop)
-        if ((st = synth(s0, s1, (const uint64_t *)c->plan, 0, hbuf + s0 / hop, hstride, p25_stride,
-                        guard ? work + 1 : nullptr, cap)) != AFS_OK)
-          return st;
-      }
-      if (!guard) return AFS_OK;
-      HIP_TRY(c, hipEventSynchronize(c->ev_k5));
-      if ((int64_t)(uint32_t)*c->hcount <= cap) return AFS_OK;
-      // (overflow: the guarded launches did nothing, the state is still the call's initial state)
-    }
-    // Chunked path: launches of `per` samples, each K5 (the chunk's plans: dense records, or in
-    // hop mode the chunk's hop records with sample-indexed dense records) and then K1.  With
-    // AFS_PLAN_OVERLAP=1 in the environment (afs_ctx::overlap), K5 of chunk k + 1 runs on the plan
-    // stream beside K1 of chunk k instead: two plan buffers, K5 of chunk k + 1 waits until K1 of
-    // chunk k - 1 has read that buffer, K1 of chunk k waits for its plans.  K5 (80 VGPRs, 4 KB of
-    // LDS per block) fits beside K1's wave, but the measured gain (+1.4 %) came with runs where K1
-    // slowed by 9 % beside it, so the default is sequential.
-    // Dense records: `per` samples per row.  Hop mode: the compact dense records of the chunk's
-    // listed hops, slot e of the work list holding `hop` records, and every hop the chunk spans may
-    // be listed -- rows x hstride slots of hop records, hstride = the chunk's hop slots + 1 (a chunk
-    // may start inside a hop).  Chunks of whole hops are sized so that this worst case fits the
-    // budget (at least one hop per chunk: past that the budget is exceeded, not the buffer).
-    int64_t per = std::min<int64_t>(S, c->launch_cap);
-    if (hops) {
-      const int64_t slots_fit = c->plan_budget / ((int64_t)rows * hop * afs::PLAN_RECORD_BYTES) - 1;
-      per = std::min<int64_t>(per, std::max<int64_t>(1, slots_fit) * hop);
-    } else {
-      per = std::min<int64_t>(per, c->plan_budget / ((int64_t)rows * afs::PLAN_RECORD_BYTES));
-    }
-    per = std::max<int64_t>(1, per);
-    const int64_t nch = (S + per - 1) / per;
-    const int64_t hstride = afs::plan_hop_slots(0, per, hop) + 1;
-    const size_t pbytes = (size_t)rows * (size_t)(hops ? hstride * hop : per) * afs::PLAN_RECORD_BYTES;
-    if ((st = ensure(c, &c->plan, &c->plan_bytes, pbytes)) != AFS_OK) return st;
-    const bool ov = c->overlap && nch > 1;
-    if (ov && (st = ensure(c, &c->plan2, &c->plan2_bytes, pbytes)) != AFS_OK) return st;
-    void *buf[2] = {c->plan, ov ? c->plan2 : c->plan};
-    afs::tree::PlanHop *hbuf[2] = {nullptr, nullptr};
-    if (hops) {
-      const size_t hbytes = (size_t)rows * (size_t)hstride * sizeof(afs::tree::PlanHop);
-      const size_t wbytes = (size_t)afs::plan_work_bytes(rows, hstride);
-      for (int q = 0; q < (ov ? 2 : 1); ++q) {
-        if ((st = ensure(c, &c->hops[q], &c->hops_bytes[q], hbytes)) != AFS_OK) return st;
-        if ((st = ensure(c, &c->plan_work[q], &c->plan_work_bytes[q], wbytes)) != AFS_OK) return st;
-      }
-      hbuf[0] = (afs::tree::PlanHop *)c->hops[0];
-      hbuf[1] = (afs::tree::PlanHop *)c->hops[ov ? 1 : 0];
-    }
-    int64_t p25_stride = 0;
-    if ((st = p25_for(per, &p25_stride)) != AFS_OK) return st;
-    hipStream_t ps = ov ? c->plan_stream : c->stream;
-    auto plan_chunk = [&](int64_t k) -> afs_status {
-      const int64_t s0 = k * per, s1 = std::min(S, s0 + per);
-      afs::PlanArgs pa{c->dev_tab, frames, fstride, rows, hop, s0, s1, (uint64_t *)buf[k & 1], per, two, uo,
-                       hbuf[k & 1], hstride, hops ? (uint32_t *)c->plan_work[ov ? (k & 1) : 0] : nullptr, hops,
-                       (int64_t)rows * hstride};  // (hop mode: a slot for every hop of the chunk)
-      hipEvent_t e0 = prof_event(c, ps);
-      HIP_TRY(c, hops ? afs::launch_plan_hops(pa, ps) : afs::launch_plan(pa, ps));
-      prof_pair(c, e0, prof_event(c, ps), 1);
-      if (ov) HIP_TRY(c, hipEventRecord(c->ev_plan[k & 1], ps));
-      return AFS_OK;
-    };
-    if (ov) {  // (the frames may have been uploaded on the context's stream just before)
-      HIP_TRY(c, hipEventRecord(c->ev_go, c->stream));
-      HIP_TRY(c, hipStreamWaitEvent(ps, c->ev_go, 0));
-      if ((st = plan_chunk(0)) != AFS_OK) return st;
-    }
-    for (int64_t k = 0; k < nch; ++k) {
-      if (!ov) {
-        if ((st = plan_chunk(k)) != AFS_OK) return st;
-      } else {
-        if (k + 1 < nch) {
-          if (k >= 1) HIP_TRY(c, hipStreamWaitEvent(ps, c->ev_free[(k + 1) & 1], 0));
-          if ((st = plan_chunk(k + 1)) != AFS_OK) return st;
-        }
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_plan[k & 1], 0));
-      }
-      const int64_t s0 = k * per, s1 = std::min(S, s0 + per);
-      if ((st = synth(s0, s1, (const uint64_t *)buf[k & 1], per, hbuf[k & 1], hstride, p25_stride)) != AFS_OK) return st;
-      if (ov) HIP_TRY(c, hipEventRecord(c->ev_free[k & 1], c->stream));
-    }
-    return AFS_OK;
+// One synthesis call as the launch functions below see it: frame transitions 1 .. ntrans
+// (frames[row * fstride + k], k = 0 the latched frame) of `rows` distinct frame rows (B, or the
+// target sequences' trajectories: utterance u plays row frame_row[u]) at `hop` samples each, the
+// audio to out[u * ostride + s], the state the launches carry between them (the context's or a
+// session's), and K1's slot order.
+struct SynthCall {
+  const afs_frame *frames;
+  int64_t fstride;
+  int rows, ntrans, hop;
+  double *out;
+  int64_t ostride;
+  void *ws;
+  int32_t *rng;
+  void *lanes;
+  int64_t bp;
+  int B, width;
+  const int32_t *frame_row;
+  SlotOrder so;
+};
+
+// The noise-source plans one K1 launch reads: the dense records, the hop records (hop mode; K1
+// indexes them from the launch's first hop), and for the guarded launches of run_hop_call K5's count
+// of claimed slots and how many there are (the launch does nothing when *skip > skip_cap).
+struct LaunchPlans {
+  const uint64_t *plan;
+  int64_t plan_stride;
+  const afs::tree::PlanHop *hops;
+  int64_t hop_stride;
+  const uint32_t *skip = nullptr;
+  int64_t skip_cap = 0;
+};
+
+// K6's glottal-tone input: section 25's pressure per sample of a launch of `per` samples.  Laid out
+// so that every utterance's row sits at the same position in its 128-byte lines as its output row
+// (stride and base congruent to the output's modulo 16 doubles): K1 stores both through one
+// line-aligned window (tree_kernel.h).
+afs_status p25_for(afs_ctx *c, const SynthCall &call, int64_t per, int64_t *stride) {
+  *stride = per + ((call.ostride - per) % 16 + 16) % 16;
+  return ensure(c, &c->p25, &c->p25_bytes, ((size_t)call.B * (size_t)*stride + 32) * sizeof(double));
+}
+// the p25 base for the launch whose outputs start at `out`
+double *p25_row0(const afs_ctx *c, const double *out) {
+  const int64_t want = (int64_t)((reinterpret_cast<uintptr_t>(out) >> 3) & 15);
+  const int64_t have = (int64_t)((reinterpret_cast<uintptr_t>(c->p25) >> 3) & 15);
+  return (double *)c->p25 + ((want - have) % 16 + 16) % 16;
+}
+
+// K5's arguments for samples [s0, s1) of the call's frame rows, dense records into `plan`
+afs::PlanArgs plan_args(const afs_ctx *c, const afs_frame *frames, int64_t fstride, int rows, int hop, int64_t s0,
+                        int64_t s1, uint64_t *plan, int64_t plan_stride) {
+  return afs::PlanArgs{c->dev_tab, frames, fstride, rows, hop, s0, s1, plan, plan_stride,
+                       c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0, c->dev_tab->consts.sec};
+}
+
+// K1 over samples [s0, s1) of the call, then K6 over them (both timed).
+afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, int64_t s1, const LaunchPlans &lp,
+                               int64_t p25_stride) {
+  const SlotOrder &so = call.so;
+  double *out = call.out + s0, *p25 = p25_row0(c, out);
+  afs::TreeArgs a{c->dev_tab, call.frames, call.fstride, call.frame_row, call.hop, s0, s1, out, call.ostride, lp.plan,
+                  lp.plan_stride, call.lanes, (double *)call.ws, call.B, c->host_tab.uni, lp.hops, lp.hop_stride, p25,
+                  p25_stride, so.order, so.variants ? 1 : 0, so.grid, so.variants_dev, lp.skip, lp.skip_cap};
+  {  // the pairs' STAT priority mode by the launch's rounds of workgroups per CU slot (two per CU):
+     // mode 2 from two rounds, 0 below (profiles/r06_pair_ab.txt r06zh-r06zm)
+    const int64_t blocks = so.grid > 0 ? so.grid : ((int64_t)call.B + afs::TREE_UPB - 1) / afs::TREE_UPB;
+    const int64_t slots = std::max<int64_t>(1, c->simds / 2), rounds = (blocks + slots - 1) / slots;
+    a.stat_prio = (call.width == afs::TREE_W && rounds >= 2) ? 2 : 0;
   }
-  const int per = (int)std::max<int64_t>(1, 8192 / std::max(1, hop));
-  for (int k = 1; k <= ntrans; k += per) {
-    const int ke = std::min(ntrans + 1, k + per);
-    double *o = out + (int64_t)(k - 1) * hop;
-    afs::LaneArgs a{c->dev_tab, frames, fstride, frame_row, k, ke, hop, o, ostride, (double *)ws, rng, bp, B,
-                    c->cfg.solver == AFS_SOLVER_SOR ? 1 : 0};
+  hipEvent_t e1 = prof_event(c);
+  HIP_TRY(c, afs::launch_tree_synth(a, call.width, c->stream));
+  hipEvent_t e2 = prof_event(c);
+  prof_pair(c, e1, e2, 0);
+  // K6: the glottal-tone filter and the output stage of the launch's samples
+  HIP_TRY(c, afs::launch_tree_output(c->dev_tab, (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
+                                     c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap));
+  prof_pair(c, e2, prof_event(c), 2);
+  return AFS_OK;
+}
+
+// hop mode: hop records from K5 (tree solver, hops >= PLAN_HOP_MIN, not AFS_PLAN_DENSE=1)
+bool hop_mode(const afs_ctx *c, int hop) { return !c->plan_dense && hop >= afs::tree::PLAN_HOP_MIN; }
+
+// The hop records and K5's work list for `rows` rows of `hstride` hop slots.
+afs_status ensure_hop_buffers(afs_ctx *c, int rows, int64_t hstride) {
+  const size_t hbytes = (size_t)rows * (size_t)hstride * sizeof(afs::tree::PlanHop);
+  afs_status st = ensure(c, &c->hops, &c->hops_bytes, hbytes);
+  if (st != AFS_OK) return st;
+  return ensure(c, &c->plan_work, &c->plan_work_bytes, (size_t)afs::plan_work_bytes(rows, hstride));
+}
+
+// Hop mode's fast path: K5 decides every hop of the call first -- one record per (row, hop), the
+// hops it cannot decide at once listed -- and K5's second stage decides the listed hops sample by
+// sample, writing the dense records of the mixed ones (whose samples differ) into a compact array
+// (one hop-long slot each, claimed from a counter).  K1 then runs the call in launches of up to
+// 65536 samples, each hop's words evaluated from its record (or read from its dense slot).  One K1
+// launch per second of 44.1 kHz audio instead of one per 4096 samples: no state save / restore and
+// launch tail in between (+0.6 %, profiles/r04c_store_launch_ab.txt).
+// *done = false: nothing ran that changed the state, and the caller runs the chunked path -- the
+// call is not in hop mode, its hop records would exceed the plan budget, or its mixed hops
+// overflowed the slots (below).
+afs_status run_hop_call(afs_ctx *c, const SynthCall &call, bool *done) {
+  *done = false;
+  const int rows = call.rows, hop = call.hop;
+  const int64_t S = (int64_t)call.ntrans * hop;
+  const int64_t hstride = afs::plan_hop_slots(0, S, hop);  // (the hops of the call)
+  const int64_t hbytes = (int64_t)rows * hstride * (int64_t)sizeof(afs::tree::PlanHop);
+  if (!hop_mode(c, hop) || hbytes > c->plan_budget) return AFS_OK;
+  afs_status st;
+  if ((st = ensure_hop_buffers(c, rows, hstride)) != AFS_OK) return st;
+  afs::tree::PlanHop *hbuf = (afs::tree::PlanHop *)c->hops;
+  uint32_t *work = (uint32_t *)c->plan_work;
+  afs::PlanArgs pa = plan_args(c, call.frames, call.fstride, rows, hop, 0, S, nullptr, 0);
+  pa.hops = hbuf;
+  pa.hop_stride = hstride;
+  pa.work = work;
+  pa.compact = true;
+  hipEvent_t e0 = prof_event(c);
+  HIP_TRY(c, afs::launch_plan_hops_iv(pa, c->stream));
+  // Slots for the mixed hops: one for every hop of the call when they fit the budget (small calls:
+  // real-time sessions, short batches), else the budget's worth.  No host read-back before K1: the
+  // launches are queued at once, guarded by the count of slots K5's second stage claimed (they do
+  // nothing if it exceeds the slots); the host then waits for K5 alone -- the launches are already
+  // queued behind it, so the device never idles for the host -- and, in the rare call whose mixed
+  // hops overflowed the slots, queues the chunked path (most listed hops are not mixed: near-ties
+  // decided alike by every sample; static vowels have none).
+  const int64_t slot_bytes = (int64_t)hop * afs::PLAN_RECORD_BYTES;
+  const int64_t every = (int64_t)rows * hstride;
+  const bool small = every * slot_bytes <= std::min<int64_t>(c->plan_budget, SMALL_CALL_DENSE_BYTES);
+  const int64_t cap = small ? every : std::min<int64_t>(every, std::max<int64_t>(1, c->plan_budget / slot_bytes));
+  if ((st = ensure(c, &c->plan, &c->plan_bytes, (size_t)(cap * slot_bytes))) != AFS_OK) return st;
+  pa.plan = (uint64_t *)c->plan;
+  pa.dense_cap = cap;
+  HIP_TRY(c, afs::launch_plan_hops_wave(pa, c->stream));
+  const bool guard = cap < every;
+  if (guard) {
+    HIP_TRY(c, hipMemcpyAsync(c->hcount, work + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_k5, c->stream));
+  }
+  prof_pair(c, e0, prof_event(c), 1);
+  const int64_t per = std::min<int64_t>(S, c->launch_cap);
+  int64_t p25_stride = 0;
+  if ((st = p25_for(c, call, per, &p25_stride)) != AFS_OK) return st;
+  for (int64_t s0 = 0; s0 < S; s0 += per) {
+    const LaunchPlans lp{(const uint64_t *)c->plan, 0, hbuf + s0 / hop, hstride, guard ? work + 1 : nullptr, cap};
+    if ((st = launch_synth_output(c, call, s0, std::min(S, s0 + per), lp, p25_stride)) != AFS_OK) return st;
+  }
+  if (guard) {
+    HIP_TRY(c, hipEventSynchronize(c->ev_k5));
+    // (overflow: the guarded launches did nothing, the state is still the call's initial state)
+    if ((int64_t)(uint32_t)*c->hcount > cap) return AFS_OK;
+  }
+  *done = true;
+  return AFS_OK;
+}
+
+// The chunked path (hops < PLAN_HOP_MIN, AFS_PLAN_DENSE=1, or past the plan budget): launches of
+// `per` samples, each K5 (the chunk's plans: dense records, or in hop mode the chunk's hop records
+// with compact dense records) and then K1, on the one stream.  (K5 of the next chunk on a second
+// stream beside K1 of this one was measured and not kept: +1.4 % in one run, K1 9 % slower beside
+// it in others, profiles/r03m_kernel_stats.csv, AB_LOG.md.)
+// Dense records: `per` samples per row.  Hop mode: the compact dense records of the chunk's
+// listed hops, slot e of the work list holding `hop` records, and every hop the chunk spans may
+// be listed -- rows x hstride slots of hop records, hstride = the chunk's hop slots + 1 (a chunk
+// may start inside a hop).  Chunks of whole hops are sized so that this worst case fits the
+// budget (at least one hop per chunk: past that the budget is exceeded, not the buffer).
+afs_status run_chunked(afs_ctx *c, const SynthCall &call) {
+  const int rows = call.rows, hop = call.hop;
+  const int64_t S = (int64_t)call.ntrans * hop;
+  const bool hops = hop_mode(c, hop);
+  int64_t per = std::min<int64_t>(S, c->launch_cap);
+  if (hops) {
+    const int64_t slots_fit = c->plan_budget / ((int64_t)rows * hop * afs::PLAN_RECORD_BYTES) - 1;
+    per = std::min<int64_t>(per, std::max<int64_t>(1, slots_fit) * hop);
+  } else {
+    per = std::min<int64_t>(per, c->plan_budget / ((int64_t)rows * afs::PLAN_RECORD_BYTES));
+  }
+  per = std::max<int64_t>(1, per);
+  const int64_t hstride = afs::plan_hop_slots(0, per, hop) + 1;
+  const size_t pbytes = (size_t)rows * (size_t)(hops ? hstride * hop : per) * afs::PLAN_RECORD_BYTES;
+  afs_status st;
+  if ((st = ensure(c, &c->plan, &c->plan_bytes, pbytes)) != AFS_OK) return st;
+  if (hops && (st = ensure_hop_buffers(c, rows, hstride)) != AFS_OK) return st;
+  int64_t p25_stride = 0;
+  if ((st = p25_for(c, call, per, &p25_stride)) != AFS_OK) return st;
+  afs::tree::PlanHop *hbuf = hops ? (afs::tree::PlanHop *)c->hops : nullptr;
+  for (int64_t s0 = 0; s0 < S; s0 += per) {
+    const int64_t s1 = std::min(S, s0 + per);
+    afs::PlanArgs pa = plan_args(c, call.frames, call.fstride, rows, hop, s0, s1, (uint64_t *)c->plan, per);
+    pa.hops = hbuf;
+    pa.hop_stride = hstride;
+    pa.work = hops ? (uint32_t *)c->plan_work : nullptr;
+    pa.compact = hops;
+    pa.dense_cap = (int64_t)rows * hstride;  // (hop mode: a slot for every hop of the chunk)
+    hipEvent_t e0 = prof_event(c);
+    HIP_TRY(c, hops ? afs::launch_plan_hops(pa, c->stream) : afs::launch_plan(pa, c->stream));
+    prof_pair(c, e0, prof_event(c), 1);
+    const LaunchPlans lp{(const uint64_t *)c->plan, per, hbuf, hstride};
+    if ((st = launch_synth_output(c, call, s0, s1, lp, p25_stride)) != AFS_OK) return st;
+  }
+  return AFS_OK;
+}
+
+// The one-lane solvers: launches of at most 8192 samples, whole transitions each.
+afs_status run_lane(afs_ctx *c, const SynthCall &call) {
+  const int per = (int)std::max<int64_t>(1, 8192 / std::max(1, call.hop));
+  for (int k = 1; k <= call.ntrans; k += per) {
+    const int ke = std::min(call.ntrans + 1, k + per);
+    double *o = call.out + (int64_t)(k - 1) * call.hop;
+    afs::LaneArgs a{c->dev_tab, call.frames, call.fstride, call.frame_row, k, ke, call.hop, o, call.ostride,
+                    (double *)call.ws, call.rng, call.bp, call.B, c->cfg.solver == AFS_SOLVER_SOR ? 1 : 0};
     hipEvent_t e0 = prof_event(c);
     HIP_TRY(c, afs::launch_lane_synth(a, c->stream));
     prof_pair(c, e0, prof_event(c), 0);
   }
   return AFS_OK;
+}
+
+// Queue the call's synthesis in launches that keep each kernel well below a second; the state is
+// carried between launches.
+afs_status run_call(afs_ctx *c, const SynthCall &call) {
+  if (!tree(c)) return run_lane(c, call);
+  bool done = false;
+  const afs_status st = run_hop_call(c, call, &done);
+  if (st != AFS_OK || done) return st;
+  return run_chunked(c, call);
 }
 
 // bytes of the state buffers for B utterances
@@ -395,6 +403,86 @@ afs_status nonfinite_report(afs_ctx *c, void *ws, int64_t bp, int B, uint8_t *fl
   if (*host_sync) HIP_TRY(c, hipMemcpyAsync(flags, dflags, (size_t)B, hipMemcpyDeviceToHost, c->stream));
   if (want_count) HIP_TRY(c, hipMemcpyAsync(c->hcount, c->dcount, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   return AFS_OK;
+}
+
+// ---- call staging: the host-or-device arguments of the calls, the context's state, the report ----
+
+// `p` when it is device memory; else (*host set) the context's buffer *buf grown to `bytes`, which
+// the caller copies to or from.
+template <class T>
+afs_status device_or_stage(afs_ctx *c, T *p, size_t bytes, void **buf, size_t *cap, T **d, bool *host) {
+  *d = p;
+  *host = !is_device_ptr(p);
+  if (!*host) return AFS_OK;
+  const afs_status s = ensure(c, buf, cap, bytes);
+  *d = (T *)*buf;
+  return s;
+}
+
+// frames[n] on the device: a host array is uploaded through the context's staging buffer
+afs_status frames_to_device(afs_ctx *c, const afs_frame *frames, size_t n, const afs_frame **d) {
+  const size_t bytes = n * sizeof(afs_frame);
+  bool host;
+  const afs_status s = device_or_stage(c, frames, bytes, &c->stage_in, &c->stage_in_bytes, d, &host);
+  if (s != AFS_OK) return s;
+  if (host) HIP_TRY(c, hipMemcpyAsync(c->stage_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
+  return AFS_OK;
+}
+
+// seeds[B] on the device likewise (null stays null: the reset kernels seed utterance u with u + 1)
+afs_status seeds_to_device(afs_ctx *c, const uint32_t *seeds, int B, const uint32_t **d) {
+  *d = nullptr;
+  if (!seeds) return AFS_OK;
+  const size_t bytes = (size_t)B * sizeof(uint32_t);
+  bool host;
+  const afs_status s = device_or_stage(c, seeds, bytes, &c->stage_seeds, &c->stage_seeds_bytes, d, &host);
+  if (s != AFS_OK) return s;
+  if (host) HIP_TRY(c, hipMemcpyAsync(c->stage_seeds, seeds, bytes, hipMemcpyHostToDevice, c->stream));
+  return AFS_OK;
+}
+
+// where the kernels write out[n]: `out` itself, or the context's staging buffer for a host array
+afs_status device_out(afs_ctx *c, double *out, size_t n, double **d, bool *host) {
+  return device_or_stage(c, out, n * sizeof(double), &c->stage_out, &c->stage_out_bytes, d, host);
+}
+
+// the context's state buffers for B utterances of `width` lanes, grown as needed and reset to the seeds
+afs_status fresh_state(afs_ctx *c, int B, int width, const uint32_t *dseeds) {
+  const int64_t bp = pad64(B);
+  afs_status s;
+  if ((s = ensure(c, &c->ws, &c->ws_bytes, ws_bytes_for(c, bp))) != AFS_OK) return s;
+  if ((s = ensure(c, (void **)&c->rng, &c->rng_bytes, (size_t)(32 * bp) * sizeof(int32_t))) != AFS_OK) return s;
+  if (tree(c) && (s = ensure(c, &c->tree_lanes, &c->tree_lanes_bytes, lanes_bytes_for(c, bp, width))) != AFS_OK)
+    return s;
+  return reset_state(c, c->ws, c->rng, c->tree_lanes, bp, B, dseeds, width);
+}
+
+// the report of a call whose kernels ran between ev0 and ev1 (after the stream has synchronised)
+afs_status fill_report(afs_ctx *c, afs_report *rep, int64_t samples) {
+  if (!rep) return AFS_OK;
+  float ms = 0.f;
+  HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  rep->device_ms = ms;
+  rep->samples = samples;
+  rep->nonfinite_utterances = *c->hcount;
+  rep->kernel = c->cfg.solver;
+  return AFS_OK;
+}
+
+// The end of a whole-trajectory call on the context's state: ev1, the non-finite flags and count, the
+// copy of staged audio to a host `out`, then the wait and the report.  The call returns without a
+// wait only when it is asynchronous (`async`) and nothing goes to host memory: no host `out`, no
+// report, no host flags.
+afs_status finish_call(afs_ctx *c, int B, int64_t T, double *out, const double *dout, bool host_out,
+                       uint8_t *nonfinite, afs_report *rep, bool async) {
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  c->last_B = B;
+  bool nf_sync = false;
+  afs_status s = nonfinite_report(c, c->ws, pad64(B), B, nonfinite, rep != nullptr, &nf_sync);
+  if (s != AFS_OK) return s;
+  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (!async || host_out || rep || nf_sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return fill_report(c, rep, (int64_t)B * T);
 }
 
 afs_status draws_of(afs_ctx *c, const void *ws, int B, int64_t *draws) {
@@ -466,7 +554,6 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
   }
   afs::build_tables(&ctx->host_tab, c.sampling_rate_hz, c.options);
   if (ctx->host_tab.n_rounds <= 0) { afs_destroy(ctx); return AFS_ERR_UNSUPPORTED; }
-  afs_status st = AFS_OK;
   auto bail = [&](afs_status s) { afs_destroy(ctx); return s; };
   if (hipMalloc((void **)&ctx->dev_tab, sizeof(afs::Tables)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
   if (hipMemcpy(ctx->dev_tab, &ctx->host_tab, sizeof(afs::Tables), hipMemcpyHostToDevice) != hipSuccess)
@@ -481,28 +568,19 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
   if (afs::preload_tree_kernels() != hipSuccess || afs::preload_plan_kernels() != hipSuccess ||
       afs::preload_audio_kernels() != hipSuccess)
     return bail(AFS_ERR_HIP);
-  if (const char *e = std::getenv("AFS_PLAN_OVERLAP")) ctx->overlap = std::atoi(e) != 0;
+  if (hipEventCreateWithFlags(&ctx->ev_k5, hipEventDisableTiming) != hipSuccess) return bail(AFS_ERR_HIP);
   if (const char *e = std::getenv("AFS_PLAN_DENSE")) ctx->plan_dense = std::atoi(e) != 0;
-  if (const char *e = std::getenv("AFS_XCD_ORDER")) ctx->xcd_order = std::atoi(e) != 0;
   if (const char *e = std::getenv("AFS_SHAPE_ORDER")) ctx->shape_order = std::atoi(e) != 0;
   if (const char *e = std::getenv("AFS_NOISE_VARIANTS")) ctx->noise_variants = std::atoi(e);
-  if (const char *e = std::getenv("AFS_CLASS_ORDER")) ctx->class_order = std::atoi(e);
-  if (const char *e = std::getenv("AFS_STAT_PRIO")) ctx->stat_prio = std::atoi(e);
   if (const char *e = std::getenv("AFS_LAUNCH_SAMPLES")) {  // (A/B and latency studies: samples per K1 launch)
     const long long v = std::atoll(e);
     if (v > 0) ctx->launch_cap = std::min<int64_t>(v, 65536);
   }
-  if (hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking) != hipSuccess) return bail(AFS_ERR_HIP);
-  for (hipEvent_t *e : {&ctx->ev_go, &ctx->ev_plan[0], &ctx->ev_plan[1], &ctx->ev_free[0], &ctx->ev_free[1], &ctx->ev_k5})
-    if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(AFS_ERR_HIP);
-  {
-    ctx->plan_budget = PLAN_BUDGET_DEFAULT;
-    if (const char *e = std::getenv("AFS_PLAN_BUDGET_MB")) {
-      const long long mb = std::atoll(e);
-      if (mb > 0) ctx->plan_budget = (int64_t)mb << 20;
-    }
+  ctx->plan_budget = PLAN_BUDGET_DEFAULT;
+  if (const char *e = std::getenv("AFS_PLAN_BUDGET_MB")) {
+    const long long mb = std::atoll(e);
+    if (mb > 0) ctx->plan_budget = (int64_t)mb << 20;
   }
-  (void)st;
   *out = ctx;
   return AFS_OK;
 }
@@ -510,36 +588,14 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
 void afs_destroy(afs_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
+  for (void **buf : c->grown)  // (every buffer of the context that ensure() allocated)
+    if (*buf) (void)hipFree(*buf);
   if (c->dev_tab) (void)hipFree(c->dev_tab);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->rng) (void)hipFree(c->rng);
-  if (c->tree_lanes) (void)hipFree(c->tree_lanes);
-  if (c->stage_in) (void)hipFree(c->stage_in);
-  if (c->stage_out) (void)hipFree(c->stage_out);
-  if (c->stage_seeds) (void)hipFree(c->stage_seeds);
-  if (c->tgt) (void)hipFree(c->tgt);
-  if (c->keys) (void)hipFree(c->keys);
-  if (c->order_buf) (void)hipFree(c->order_buf);
-  if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-  if (c->plan_stream) (void)hipStreamSynchronize(c->plan_stream);
-  if (c->plan) (void)hipFree(c->plan);
-  if (c->plan2) (void)hipFree(c->plan2);
-  for (void *h : c->hops)
-    if (h) (void)hipFree(h);
-  for (void *w : c->plan_work)
-    if (w) (void)hipFree(w);
-  if (c->p25) (void)hipFree(c->p25);
-  if (c->plan_stream) (void)hipStreamDestroy(c->plan_stream);
-  for (hipEvent_t e : {c->ev_go, c->ev_plan[0], c->ev_plan[1], c->ev_free[0], c->ev_free[1], c->ev_k5})
-    if (e) (void)hipEventDestroy(e);
-  if (c->stage_nf) (void)hipFree(c->stage_nf);
   if (c->dcount) (void)hipFree(c->dcount);
   if (c->hcount) (void)hipHostFree(c->hcount);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
+  for (hipEvent_t e : {c->ev_k5, c->ev0, c->ev1})
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
-  for (void *p : {c->m_out, c->m_pcm, c->m_nf, c->m_root})
-    if (p) (void)hipFree(p);
   delete c;
 }
 
@@ -577,95 +633,34 @@ afs_status afs_synchronize(afs_ctx *c) {
 // fricatives (16 waves per SIMD, the classes in long runs of the slot order) +0.7 %, at 32768 (8 per
 // SIMD) +0.05 % (profiles/r05i_fricatives_variants_ab.txt, r05k_variant_rule_ab.txt,
 // r05r_variant_rule_ab.txt).  Without them the class is left out of the sort (the class key alone
-// measured -0.6 %, r05f_variant_order_ab.txt).  (AFS_CLASS_ORDER=3, an A/B study, deals the blocks to
-// the XCDs on the host.)
+// measured -0.6 %, r05f_variant_order_ab.txt).  (Dealing the blocks of a class-major order to the XCDs
+// on the host, one variant per XCD, cost a host wait and measured 311 M against 425 M samples/s:
+// profiles/r05j_xcd_deal_static_ab.txt, AB_LOG.md.)
 static afs_status shape_order(afs_ctx *c, const afs_frame *dframes, int64_t fstride, int B, int width, SlotOrder *so) {
   *so = plain_order(c);
   const int upb = afs::TREE_UPB;
   if (!tree(c) || !c->shape_order || width == afs::TREE_VOICE_W || B <= upb) return AFS_OK;
   const int nb = (B + upb - 1) / upb;
-  const bool by_xcd = c->class_order == 3 && c->noise_variants != 0;
   afs_status s;
   // keys[B], sorted keys[B], indices[B], the variant flag
   const size_t kb = (size_t)B * (2 * sizeof(uint64_t) + sizeof(int32_t)) + 16;
   if ((s = ensure(c, &c->keys, &c->keys_bytes, kb)) != AFS_OK) return s;
-  uint64_t *dkeys = (uint64_t *)c->keys;
-  HIP_TRY(c, afs::launch_utterance_keys(dframes, fstride, B, dkeys, by_xcd ? 1 : (c->class_order == 3 ? 0 : c->class_order),
-                                        c->stream));
-  if (!by_xcd) {
-    uint64_t *dsorted = dkeys + B;
-    int32_t *didx = (int32_t *)(dsorted + B);
-    int32_t *dvar = didx + B;
-    const int shift = c->class_order == 1 ? 48 : c->class_order == 2 ? 40 : -1;
-    const int64_t waves_per_simd = (int64_t)B / ((int64_t)(64 / afs::TREE_W) * std::max(1, c->simds));
-    const int mode = c->noise_variants == 0 ? 0 : c->noise_variants == 1 ? 1 : 2;
-    if ((s = ensure(c, &c->order_buf, &c->order_bytes, (size_t)nb * upb * sizeof(int32_t))) != AFS_OK) return s;
-    size_t tb = 0;
-    HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, shift, mode, waves_per_simd >= 16, dvar,
-                                      (int32_t *)c->order_buf, nb * upb, nullptr, &tb, c->stream));
-    if ((s = ensure(c, &c->sort_tmp, &c->sort_tmp_bytes, tb + 256)) != AFS_OK) return s;
-    tb = c->sort_tmp_bytes;
-    HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, shift, mode, waves_per_simd >= 16, dvar,
-                                      (int32_t *)c->order_buf, nb * upb, c->sort_tmp, &tb, c->stream));
-    so->order = (const int32_t *)c->order_buf;
-    so->grid = nb;
-    so->variants_dev = dvar;
-    return AFS_OK;
-  }
-  c->hkeys.resize((size_t)B);
-  HIP_TRY(c, hipMemcpyAsync(c->hkeys.data(), dkeys, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::vector<int32_t> idx((size_t)B);
-  for (int u = 0; u < B; ++u) idx[(size_t)u] = u;
-  std::stable_sort(idx.begin(), idx.end(),
-                   [&](int32_t a, int32_t b) { return c->hkeys[(size_t)a] < c->hkeys[(size_t)b]; });
-  int nblocks = nb;
-  {
-    // The blocks of the class-major order (the full noise phases first) dealt to the 8 XCDs in
-    // contiguous runs of equal expected cost, so that the blocks one XCD runs -- whose waves share
-    // its CUs' instruction caches -- run one noise-phase variant (at most one change per XCD): a
-    // CU pair holds about one copy of the kernel body, and waves of different variants on it
-    // slowed each other (profiles/r05i_fricatives_variants_ab.txt).  Blocks are dealt to XCDs
-    // round-robin (block b runs on XCD b % 8, MI355X_MICROARCH.md), so run x occupies grid
-    // blocks x, x + 8, ...; the shorter runs end in empty blocks, which exit at once.  Expected
-    // cost of a block: that of its heaviest utterance's variant, from the ceilings measured with
-    // every wave in one variant (profiles/r05b_noise_variant_ceiling_ab.txt).
-    constexpr int XCDS = 8;
-    static const double cost[4] = {1.0, 0.976, 0.954, 0.885};  // NZ_FULL, NZ_T1ALL, NZ_TONGUE1, NZ_GLOTTIS
-    std::vector<double> bc((size_t)nb, 0.0);
-    double total = 0.0;
-    for (int b = 0; b < nb; ++b) {
-      double w = 0.0;
-      for (int g = 0; g < upb && b * upb + g < B; ++g)
-        w = std::max(w, cost[(c->hkeys[(size_t)idx[(size_t)(b * upb + g)]] >> 48) & 3]);
-      bc[(size_t)b] = w;
-      total += w;
-    }
-    std::vector<int> first(XCDS + 1, nb);
-    first[0] = 0;
-    double acc = 0.0;
-    int x = 1;
-    for (int b = 0; b < nb && x < XCDS; ++b) {
-      acc += bc[(size_t)b];
-      if (acc >= total * x / XCDS) first[(size_t)x++] = b + 1;
-    }
-    for (; x < XCDS; ++x) first[(size_t)x] = nb;
-    int len = 0;
-    for (int q = 0; q < XCDS; ++q) len = std::max(len, first[(size_t)q + 1] - first[(size_t)q]);
-    nblocks = XCDS * len;
-    c->horder.assign((size_t)nblocks * upb, B);
-    for (int q = 0; q < XCDS; ++q)
-      for (int b = first[(size_t)q]; b < first[(size_t)q + 1]; ++b) {
-        const int slot = (q + XCDS * (b - first[(size_t)q])) * upb;
-        for (int g = 0; g < upb && b * upb + g < B; ++g) c->horder[(size_t)(slot + g)] = idx[(size_t)(b * upb + g)];
-      }
-  }
-  const size_t obytes = c->horder.size() * sizeof(int32_t);
-  if ((s = ensure(c, &c->order_buf, &c->order_bytes, obytes)) != AFS_OK) return s;
-  HIP_TRY(c, hipMemcpyAsync(c->order_buf, c->horder.data(), obytes, hipMemcpyHostToDevice, c->stream));
+  uint64_t *dkeys = (uint64_t *)c->keys, *dsorted = dkeys + B;
+  int32_t *didx = (int32_t *)(dsorted + B), *dvar = didx + B;
+  HIP_TRY(c, afs::launch_utterance_keys(dframes, fstride, B, dkeys, c->stream));
+  const int64_t waves_per_simd = (int64_t)B / ((int64_t)(64 / afs::TREE_W) * std::max(1, c->simds));
+  const int mode = c->noise_variants == 0 ? 0 : c->noise_variants == 1 ? 1 : 2;
+  if ((s = ensure(c, &c->order_buf, &c->order_bytes, (size_t)nb * upb * sizeof(int32_t))) != AFS_OK) return s;
+  size_t tb = 0;  // (the first call asks for the sort's scratch size only)
+  HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, mode, waves_per_simd >= 16, dvar,
+                                    (int32_t *)c->order_buf, nb * upb, nullptr, &tb, c->stream));
+  if ((s = ensure(c, &c->sort_tmp, &c->sort_tmp_bytes, tb + 256)) != AFS_OK) return s;
+  tb = c->sort_tmp_bytes;
+  HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, mode, waves_per_simd >= 16, dvar,
+                                    (int32_t *)c->order_buf, nb * upb, c->sort_tmp, &tb, c->stream));
   so->order = (const int32_t *)c->order_buf;
-  so->grid = nblocks;
-  so->variants = true;
+  so->grid = nb;
+  so->variants_dev = dvar;
   return AFS_OK;
 }
 
@@ -677,57 +672,21 @@ static afs_status synth_core(afs_ctx *c, const afs_frame *frames, const uint32_t
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int64_t T = (int64_t)(F - 1) * hop;
-  const int64_t bp = pad64(B);
   afs_status s;
-  // inputs
-  const afs_frame *dframes = frames;
-  if (!is_device_ptr(frames)) {
-    size_t bytes = (size_t)B * F * sizeof(afs_frame);
-    if ((s = ensure(c, &c->stage_in, &c->stage_in_bytes, bytes)) != AFS_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(c->stage_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
-    dframes = (const afs_frame *)c->stage_in;
-  }
-  const uint32_t *dseeds = seeds;
-  if (seeds && !is_device_ptr(seeds)) {
-    if ((s = ensure(c, &c->stage_seeds, &c->stage_seeds_bytes, (size_t)B * 4)) != AFS_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(c->stage_seeds, seeds, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
-    dseeds = (const uint32_t *)c->stage_seeds;
-  }
-  double *dout = out;
-  const bool host_out = !is_device_ptr(out);
-  if (host_out) {
-    if ((s = ensure(c, &c->stage_out, &c->stage_out_bytes, (size_t)B * T * sizeof(double))) != AFS_OK) return s;
-    dout = (double *)c->stage_out;
-  }
-  // state
+  const afs_frame *dframes;
+  const uint32_t *dseeds;
+  double *dout;
+  bool host_out;
+  if ((s = frames_to_device(c, frames, (size_t)B * F, &dframes)) != AFS_OK) return s;
+  if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
+  if ((s = device_out(c, out, (size_t)B * T, &dout, &host_out)) != AFS_OK) return s;
   const int width = lanes > 0 ? lanes : lanes_for(c, B);
-  if ((s = ensure(c, &c->ws, &c->ws_bytes, ws_bytes_for(c, bp))) != AFS_OK) return s;
-  if ((s = ensure(c, (void **)&c->rng, &c->rng_bytes, (size_t)(32 * bp) * sizeof(int32_t))) != AFS_OK) return s;
-  if (tree(c) && (s = ensure(c, &c->tree_lanes, &c->tree_lanes_bytes, lanes_bytes_for(c, bp, width))) != AFS_OK)
-    return s;
-  if ((s = reset_state(c, c->ws, c->rng, c->tree_lanes, bp, B, dseeds, width)) != AFS_OK) return s;
+  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  SlotOrder so;
-  if ((s = shape_order(c, dframes, F, B, width, &so)) != AFS_OK) return s;
-  if ((s = run_chunks(c, dframes, F, B, F - 1, hop, dout, T, c->ws, c->rng, c->tree_lanes, bp, B, width, nullptr,
-                      so)) != AFS_OK)
-    return s;
-  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-  c->last_B = B;
-  bool nf_sync = false;
-  if ((s = nonfinite_report(c, c->ws, bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return s;
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  const bool sync = !(force_async || (c->cfg.flags & AFS_ASYNC)) || host_out || rep || nf_sync;
-  if (sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (rep) {
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    rep->device_ms = ms;
-    rep->samples = (int64_t)B * T;
-    rep->nonfinite_utterances = *c->hcount;
-    rep->kernel = c->cfg.solver;
-  }
-  return AFS_OK;
+  SynthCall call{dframes, F, B, F - 1, hop, dout, T, c->ws, c->rng, c->tree_lanes, pad64(B), B, width, nullptr, {}};
+  if ((s = shape_order(c, dframes, F, B, width, &call.so)) != AFS_OK) return s;
+  if ((s = run_call(c, call)) != AFS_OK) return s;
+  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, force_async || (c->cfg.flags & AFS_ASYNC));
 }
 
 afs_status afs::synthesize_async(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
@@ -816,25 +775,14 @@ afs_status afs_noise_plans(afs_ctx *c, const afs_frame *frames, int32_t rows, in
                                              "0 <= s_begin < s_end <= (num_frames-1)*hop");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   afs_status s;
-  const afs_frame *dframes = frames;
-  if (!is_device_ptr(frames)) {
-    const size_t bytes = (size_t)rows * F * sizeof(afs_frame);
-    if ((s = ensure(c, &c->stage_in, &c->stage_in_bytes, bytes)) != AFS_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(c->stage_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
-    dframes = (const afs_frame *)c->stage_in;
-  }
+  const afs_frame *dframes;
+  if ((s = frames_to_device(c, frames, (size_t)rows * F, &dframes)) != AFS_OK) return s;
   const int64_t n = s1 - s0;
   const size_t bytes = (size_t)rows * (size_t)n * afs::PLAN_RECORD_BYTES;
-  uint64_t *dplans = plans;
-  const bool host_out = !is_device_ptr(plans);
-  if (host_out) {
-    if ((s = ensure(c, &c->plan, &c->plan_bytes, bytes)) != AFS_OK) return s;
-    dplans = (uint64_t *)c->plan;
-  }
-  afs::PlanArgs pa{c->dev_tab, dframes, F, rows, hop, s0, s1, dplans, n,
-                   c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0,
-                   c->dev_tab->consts.sec};
-  HIP_TRY(c, afs::launch_plan(pa, c->stream));
+  uint64_t *dplans;
+  bool host_out;
+  if ((s = device_or_stage(c, plans, bytes, &c->plan, &c->plan_bytes, &dplans, &host_out)) != AFS_OK) return s;
+  HIP_TRY(c, afs::launch_plan(plan_args(c, dframes, F, rows, hop, s0, s1, dplans, n), c->stream));
   if (host_out) HIP_TRY(c, hipMemcpyAsync(plans, dplans, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
@@ -852,33 +800,24 @@ afs_status afs_noise_plan_hops(afs_ctx *c, const afs_frame *frames, int32_t rows
                                              "0 <= s_begin < s_end <= (num_frames-1)*hop");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   afs_status s;
-  const afs_frame *dframes = frames;
-  if (!is_device_ptr(frames)) {
-    const size_t bytes = (size_t)rows * F * sizeof(afs_frame);
-    if ((s = ensure(c, &c->stage_in, &c->stage_in_bytes, bytes)) != AFS_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(c->stage_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
-    dframes = (const afs_frame *)c->stage_in;
-  }
+  const afs_frame *dframes;
+  if ((s = frames_to_device(c, frames, (size_t)rows * F, &dframes)) != AFS_OK) return s;
   const int64_t n = s1 - s0, slots = afs::plan_hop_slots(s0, s1, hop);
   const size_t pbytes = (size_t)rows * (size_t)n * afs::PLAN_RECORD_BYTES;
   const size_t hbytes = (size_t)rows * (size_t)slots * sizeof(afs::tree::PlanHop);
-  uint64_t *dplans = plans;
-  uint8_t *dhops = hops;
-  const bool host_plans = !is_device_ptr(plans), host_hops = !is_device_ptr(hops);
-  if (host_plans) {
-    if ((s = ensure(c, &c->plan, &c->plan_bytes, pbytes)) != AFS_OK) return s;
-    dplans = (uint64_t *)c->plan;
-    HIP_TRY(c, hipMemcpyAsync(dplans, plans, pbytes, hipMemcpyHostToDevice, c->stream));
-  }
-  if (host_hops) {
-    if ((s = ensure(c, &c->hops[0], &c->hops_bytes[0], hbytes)) != AFS_OK) return s;
-    dhops = (uint8_t *)c->hops[0];
-  }
-  if ((s = ensure(c, &c->plan_work[0], &c->plan_work_bytes[0], (size_t)afs::plan_work_bytes(rows, slots))) != AFS_OK)
+  uint64_t *dplans;
+  uint8_t *dhops;
+  bool host_plans, host_hops;
+  if ((s = device_or_stage(c, plans, pbytes, &c->plan, &c->plan_bytes, &dplans, &host_plans)) != AFS_OK) return s;
+  // (the records of the samples outside mixed hops are left as the caller passed them)
+  if (host_plans) HIP_TRY(c, hipMemcpyAsync(dplans, plans, pbytes, hipMemcpyHostToDevice, c->stream));
+  if ((s = device_or_stage(c, hops, hbytes, &c->hops, &c->hops_bytes, &dhops, &host_hops)) != AFS_OK) return s;
+  if ((s = ensure(c, &c->plan_work, &c->plan_work_bytes, (size_t)afs::plan_work_bytes(rows, slots))) != AFS_OK)
     return s;
-  afs::PlanArgs pa{c->dev_tab, dframes, F, rows, hop, s0, s1, dplans, n,
-                   c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0, c->dev_tab->consts.sec,
-                   (afs::tree::PlanHop *)dhops, slots, (uint32_t *)c->plan_work[0]};
+  afs::PlanArgs pa = plan_args(c, dframes, F, rows, hop, s0, s1, dplans, n);
+  pa.hops = (afs::tree::PlanHop *)dhops;
+  pa.hop_stride = slots;
+  pa.work = (uint32_t *)c->plan_work;
   HIP_TRY(c, afs::launch_plan_hops(pa, c->stream));
   if (host_plans) HIP_TRY(c, hipMemcpyAsync(plans, dplans, pbytes, hipMemcpyDeviceToHost, c->stream));
   if (host_hops) HIP_TRY(c, hipMemcpyAsync(hops, dhops, hbytes, hipMemcpyDeviceToHost, c->stream));
@@ -1017,13 +956,12 @@ afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32
   }
   if (!out) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize: out is NULL");
   if (n < 1) n = 1;  // Synthesizer.cpp:543-546
-  double *dout = out;
-  const bool host_out = !is_device_ptr(out);
   const size_t nout = (size_t)B * (size_t)n;
+  double *dout;
+  bool host_out;
   afs_status st;
-  if (host_out) {
-    if ((st = ensure(c, &c->stage_out, &c->stage_out_bytes, nout * sizeof(double))) != AFS_OK) return st;
-    dout = (double *)c->stage_out;
+  if ((st = device_out(c, out, nout, &dout, &host_out)) != AFS_OK) return st;
+  if (host_out) {  // (back through the session's pinned buffer)
     if (nout > s->hout_cap) {
       if (s->hout) (void)hipHostFree(s->hout);
       s->hout = nullptr;
@@ -1033,9 +971,9 @@ afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32
     }
   }
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  if ((st = run_chunks(c, s->pair, 2, B, 1, n, dout, n, s->ws, s->rng, s->tree_lanes, s->bp, B, s->lanes, nullptr,
-                       plain_order(c))) != AFS_OK)
-    return st;
+  const SynthCall call{s->pair, 2, B, 1, n, dout, n, s->ws, s->rng, s->tree_lanes, s->bp, B, s->lanes, nullptr,
+                       plain_order(c)};
+  if ((st = run_call(c, call)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   // prevTube = *newTube (Synthesizer.cpp:633-637)
   HIP_TRY(c, hipMemcpy2DAsync(s->pair, 2 * sizeof(afs_frame), s->pair + 1, 2 * sizeof(afs_frame),
@@ -1043,18 +981,10 @@ afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32
   bool nf_sync = false;
   if ((st = nonfinite_report(c, s->ws, s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
   if (host_out) HIP_TRY(c, hipMemcpyAsync(s->hout, dout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a session call always waits: its audio is due now)
   if (host_out) std::memcpy(out, s->hout, nout * sizeof(double));
   if (produced) *produced = n;
-  if (rep) {
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    rep->device_ms = ms;
-    rep->samples = (int64_t)B * n;
-    rep->nonfinite_utterances = *c->hcount;
-    rep->kernel = c->cfg.solver;
-  }
-  return AFS_OK;
+  return fill_report(c, rep, (int64_t)B * n);
 }
 
 afs_status afs_session_rng_draws(afs_session *s, int64_t *draws) {
@@ -1206,12 +1136,12 @@ afs_status afs_play_target_sequences(afs_ctx *c, const double *shapes, int32_t n
   const int width = lanes_for(c, B);
   // tree solver: the XCD-aware slot order of the utterances by trajectory (xcd_order)
   std::vector<int32_t> order;
-  if (tree(c) && c->xcd_order) {
+  if (tree(c)) {
     const int upb = width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB;
     // blocks the GPU holds at once: the voice kernel one wave (block) per SIMD, the throughput
     // kernel one wave per SIMD in blocks of TREE_WPB waves (4 / TREE_WPB blocks per CU, its LDS)
     const int conc = width == afs::TREE_VOICE_W ? c->simds : c->simds / afs::TREE_WPB;
-    order = xcd_order(row, B, upb, conc);
+    order = afs::xcd_order(row, B, upb, conc);
   }
   const size_t seq_bytes = seq.size() * sizeof(double);
   const size_t row_bytes = (size_t)B * sizeof(int32_t), ord_bytes = order.size() * sizeof(int32_t);
@@ -1223,24 +1153,12 @@ afs_status afs_play_target_sequences(afs_ctx *c, const double *shapes, int32_t n
   HIP_TRY(c, hipMemcpyAsync(drow, row.data(), row_bytes, hipMemcpyHostToDevice, c->stream));
   if (dord) HIP_TRY(c, hipMemcpyAsync(dord, order.data(), ord_bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors die with this call
-  const uint32_t *dseeds = seeds;
-  if (seeds && !is_device_ptr(seeds)) {
-    if ((s = ensure(c, &c->stage_seeds, &c->stage_seeds_bytes, (size_t)B * 4)) != AFS_OK) return s;
-    HIP_TRY(c, hipMemcpyAsync(c->stage_seeds, seeds, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
-    dseeds = (const uint32_t *)c->stage_seeds;
-  }
-  double *dout = out;
-  const bool host_out = !is_device_ptr(out);
-  if (host_out) {
-    if ((s = ensure(c, &c->stage_out, &c->stage_out_bytes, (size_t)B * T * sizeof(double))) != AFS_OK) return s;
-    dout = (double *)c->stage_out;
-  }
-  const int64_t bp = pad64(B);
-  if ((s = ensure(c, &c->ws, &c->ws_bytes, ws_bytes_for(c, bp))) != AFS_OK) return s;
-  if ((s = ensure(c, (void **)&c->rng, &c->rng_bytes, (size_t)(32 * bp) * sizeof(int32_t))) != AFS_OK) return s;
-  if (tree(c) && (s = ensure(c, &c->tree_lanes, &c->tree_lanes_bytes, lanes_bytes_for(c, bp, width))) != AFS_OK)
-    return s;
-  if ((s = reset_state(c, c->ws, c->rng, c->tree_lanes, bp, B, dseeds, width)) != AFS_OK) return s;
+  const uint32_t *dseeds;
+  double *dout;
+  bool host_out;
+  if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
+  if ((s = device_out(c, out, (size_t)B * T, &dout, &host_out)) != AFS_OK) return s;
+  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
   // time chunks of Tc samples: Tc + 1 frames per sequence (the first repeats the previous
   // chunk's last), at most 1 GiB of frames
   const int64_t budget = (int64_t)1 << 30;
@@ -1252,28 +1170,12 @@ afs_status afs_play_target_sequences(afs_ctx *c, const double *shapes, int32_t n
   for (int64_t k0 = 0; k0 < T; k0 += Tc) {
     const int nk = (int)std::min<int64_t>(Tc, T - k0);
     HIP_TRY(c, afs::launch_target_frames(dseq, Q, plan, k0, nk + 1, Tc + 1, dframes, c->stream));
-    SlotOrder so = plain_order(c);
-    so.order = dord;
-    if ((s = run_chunks(c, dframes, Tc + 1, Q, nk, 1, dout + k0, T, c->ws, c->rng, c->tree_lanes, bp, B, width,
-                        drow, so)) != AFS_OK)
-      return s;
+    SynthCall call{dframes, Tc + 1, Q, nk, 1, dout + k0, T, c->ws, c->rng, c->tree_lanes, pad64(B), B, width, drow,
+                   plain_order(c)};
+    call.so.order = dord;
+    if ((s = run_call(c, call)) != AFS_OK) return s;
   }
-  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-  c->last_B = B;
-  bool nf_sync = false;
-  if ((s = nonfinite_report(c, c->ws, bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return s;
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  const bool sync = !(c->cfg.flags & AFS_ASYNC) || host_out || rep || nf_sync;
-  if (sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (rep) {
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    rep->device_ms = ms;
-    rep->samples = (int64_t)B * T;
-    rep->nonfinite_utterances = *c->hcount;
-    rep->kernel = c->cfg.solver;
-  }
-  return AFS_OK;
+  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, (c->cfg.flags & AFS_ASYNC) != 0);
 }
 
 }  // extern "C"

@@ -17,7 +17,10 @@ struct afs_ctx {
   afs::Tables host_tab{};
   afs::Tables *dev_tab = nullptr;
   std::string err;
-  // reusable device buffers for whole-trajectory calls
+  // reusable device buffers, each grown on demand by afs::ensure(), which lists it in `grown`:
+  // afs_destroy frees what is listed
+  std::vector<void **> grown;
+  // the state of whole-trajectory calls
   void *ws = nullptr;
   size_t ws_bytes = 0;
   int32_t *rng = nullptr;
@@ -30,40 +33,31 @@ struct afs_ctx {
   size_t stage_out_bytes = 0;
   void *stage_seeds = nullptr;
   size_t stage_seeds_bytes = 0;
-  void *tgt = nullptr;  // target sequences: shape rows [Q][4][16] then frame_row [B]
+  void *tgt = nullptr;  // target sequences: shape rows [Q][4][16], frame_row [B], then the slot order
   size_t tgt_bytes = 0;
   void *plan = nullptr;   // tree solver: noise-source plans of one launch (tree_plan.h)
   size_t plan_bytes = 0;
-  void *plan2 = nullptr;  // the second plan buffer: K5 fills one while K1 reads the other
-  size_t plan2_bytes = 0;
-  void *hops[2] = {nullptr, nullptr};  // tree solver, hops >= PLAN_HOP_MIN: hop records (tree_plan.h PlanHop)
-  size_t hops_bytes[2] = {0, 0};
+  void *hops = nullptr;  // tree solver, hops >= PLAN_HOP_MIN: hop records (tree_plan.h PlanHop)
+  size_t hops_bytes = 0;
   void *p25 = nullptr;  // tree solver: section 25's pressure per sample of a launch (K6's tone input)
   size_t p25_bytes = 0;
-  void *plan_work[2] = {nullptr, nullptr};  // hop mode: K5's work lists (the hops decided sample by sample)
-  size_t plan_work_bytes[2] = {0, 0};
+  void *plan_work = nullptr;  // hop mode: K5's work list (the hops decided sample by sample)
+  size_t plan_work_bytes = 0;
+  // the environment's switches (afs_create; include/afs.h lists them)
   bool plan_dense = false;             // AFS_PLAN_DENSE=1: dense records at every hop (A/B, tests)
-  bool xcd_order = true;               // AFS_XCD_ORDER=0: shared trajectories in utterance order (A/B)
   int64_t launch_cap = 65536;          // samples per K1 launch at most (AFS_LAUNCH_SAMPLES lowers it)
   bool shape_order = true;             // AFS_SHAPE_ORDER=0: afs_synthesize's utterances in call order
   // AFS_NOISE_VARIANTS: 1 (default) K1's noise-phase variants for the calls whose slot order finds
   // at least half of the utterances in a light class (shape_order), 2 for every call, 0 never
   int noise_variants = 1;
-  int class_order = 2;                 // AFS_CLASS_ORDER: the slot order's noise-class key (af_kernels.hip; A/B)
-  int stat_prio = -1;                  // AFS_STAT_PRIO: the pairs' STAT priority mode (afs_tree.h), -1 by the launch's rounds
+  int64_t plan_budget = 0;  // bytes of plans one call may hold (AFS_PLAN_BUDGET_MB; afs_capi.cpp)
   void *keys = nullptr;                // shape keys, sorted keys, utterance indices, the variant flag (device)
   size_t keys_bytes = 0;
   void *sort_tmp = nullptr;            // the device radix sort's scratch
   size_t sort_tmp_bytes = 0;
   void *order_buf = nullptr;           // the slot order built from them (device)
   size_t order_bytes = 0;
-  std::vector<uint64_t> hkeys;
-  std::vector<int32_t> horder;
-  hipStream_t plan_stream = nullptr;  // K5 of the next launch, beside K1 of this one (overlap)
-  bool overlap = false;                // AFS_PLAN_OVERLAP=1 (afs_capi.cpp run_chunks)
-  hipEvent_t ev_go = nullptr, ev_plan[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-  hipEvent_t ev_k5 = nullptr;  // after K5 and the read-back of its claimed slots (run_chunks' guarded fast path)
-  int64_t plan_budget = 0;  // bytes of plans one launch may use (afs_capi.cpp)
+  hipEvent_t ev_k5 = nullptr;  // after K5 and the read-back of its claimed slots (run_hop_call's guarded launches)
   void *stage_nf = nullptr;  // per-utterance non-finite flags staged for a host array
   size_t stage_nf_bytes = 0;
   // afs_multi_synthesize: this device's shard of float audio, its int16 audio, its flags, and

@@ -36,26 +36,26 @@ struct TreeArgs {
   int64_t p25_stride = 0;
   // utterance of slot block * (utterances per block) + g, or the identity when null (entries >= B:
   // padding slots); shared trajectories (frame_row) order the utterances by row so that the blocks
-  // one XCD runs at a time play few rows (afs_capi.cpp xcd_order)
+  // one XCD runs at a time play few rows (afs_xcd_order.h)
   const int32_t *order = nullptr;
   // hop mode: run each wave's launch in the lightest noise-phase variant its hop records allow
   // (tree_kernel.h noise_variant; 0: always the full phases -- AFS_NOISE_VARIANTS=0, A/B and tests)
   int noise_variants = 1;
-  // blocks of the launch (0: enough for B utterances); with `order`, blocks whose slots are all
-  // padding exit at once (the XCD-dealt slot order of afs_capi.cpp shape_order)
+  // blocks of the launch (0: enough for B utterances; afs_capi.cpp shape_order passes that count);
+  // with `order`, blocks whose slots are all padding exit at once
   int grid_blocks = 0;
   // the variant rule decided on the device (afs_capi.cpp shape_order: the call's slot order sorted
   // on the device): when set, *variants_dev replaces noise_variants
   const int32_t *variants_dev = nullptr;
-  // hop mode with compact slots that may not hold every mixed hop (afs_capi.cpp run_chunks): the
+  // hop mode with compact slots that may not hold every mixed hop (afs_capi.cpp run_hop_call): the
   // launch does nothing when K5 claimed more than skip_cap slots (*skip_claims > skip_cap); the host
   // then runs the call through the chunked path instead
   const uint32_t *skip_claims = nullptr;
   int64_t skip_cap = 0;
   // wave pairs: when the STAT waves run at a higher issue priority than their SIMDs' DYN waves
   // (s_setprio; tree_core.h sample_step_pair): 0 never, 1 during the solver, 2 during the first
-  // phase group and the solver, 3 the whole launch (afs_capi.cpp picks by the launch's rounds of
-  // workgroups per CU slot; profiles/r06_pair_ab.txt r06zh-r06zm)
+  // phase group and the solver, 3 the whole launch (afs_capi.cpp launch_synth_output: 2 from two
+  // rounds of workgroups per CU slot, 0 below; profiles/r06_pair_ab.txt r06zh-r06zm)
   int stat_prio = 0;
 };
 // K5: the noise-source plans of samples [s_begin, s_end) of `rows` frame rows.

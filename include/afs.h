@@ -111,12 +111,21 @@ typedef struct afs_options {
   double flow_separation_area_ratio; /* 1.0 */
 } afs_options;
 
-/* Calls return once their work is queued on the context's stream.  One exception: a large tree call
- * (its mixed hops' noise plans may overflow the plan budget) reads back how many plan slots K5
- * claimed, after its synthesis launches are queued (guarded on the device: they do nothing on an
- * overflow, and the call then queues its chunked path).  That wait covers the work queued before K5,
- * the previous call's synthesis included, but the device does not idle: this call's synthesis is
- * queued behind K5.  The slot order is sorted on the device, with no read-back. */
+/* afs_synthesize, afs_play_target_sequences and afs_to_int16 return once their work is queued on the
+ * context's stream.  These cases still wait on the host:
+ *   - afs_play_target_sequences, once, early: for the upload of the trajectories' shape rows and slot
+ *     order, which it builds in host memory of its own (the synthesis is queued after that wait);
+ *   - a host `out` (the audio is copied back before the call returns), and host input or output
+ *     of afs_to_int16;
+ *   - a report (its device time and non-finite count are read when the work is done);
+ *   - host `nonfinite` flags (device flags do not wait);
+ *   - a large tree call whose mixed hops' noise plans may overflow the plan budget: it reads back how
+ *     many plan slots K5 claimed, after its synthesis launches are queued (guarded on the device: they
+ *     do nothing on an overflow, and the call then queues its chunked path).  That wait covers the
+ *     work queued before K5, the previous call's synthesis included, but the device does not idle:
+ *     this call's synthesis is queued behind K5.
+ * The slot order is sorted on the device, with no read-back.  Sessions, the diagnostics and
+ * afs_af_to_frames always wait. */
 #define AFS_ASYNC 0x1u
 /* Record an event pair around every kernel launch of the synthesis calls; afs_kernel_times
  * returns their summed durations (measurement only: a few microseconds per launch). */
@@ -175,19 +184,16 @@ int32_t afs_abi_version(void);
  *                           records per row (2 x hop x 128 B x rows) even when that exceeds N MB
  *   AFS_LAUNCH_SAMPLES=N    samples per synthesis-kernel launch at most (default 65536; the state
  *                           crosses launches, the audio is the same bit for bit)
- *   AFS_XCD_ORDER=0         shared trajectories (target sequences) in utterance order instead of
- *                           the XCD-aware order
- *   AFS_SHAPE_ORDER=0       afs_synthesize's utterances in call order in the 16-lane kernel's
+ *   AFS_SHAPE_ORDER=0      afs_synthesize's utterances in call order in the 16-lane kernel's
  *                           slots instead of sorted by the shape of their first frame (the audio
  *                           of each utterance is the same either way)
  *   AFS_NOISE_VARIANTS=0    the synthesis kernel always runs its full noise phases instead of the
  *                           lightest variant each launch's noise-source plans allow (same audio);
  *                           =2 the variants for every call (default: for calls whose batch is mostly
  *                           light or holds >= 16 waves per SIMD: DESIGN.md 2.5)
- *   AFS_PLAN_OVERLAP=1      chunked path: K5 of the next launch beside K1 of this one
- *   AFS_STAT_PRIO=0..3      when the throughput kernel's STAT waves run at the higher issue priority:
- *                           never / the solver / the first phase group and the solver / always
- *                           (default: 2 for launches of two or more rounds of workgroups per CU) */
+ * (Settled and no longer switches -- the XCD-aware slot order of shared trajectories, the noise
+ * class's place in the shape key, the STAT waves' issue priority by the launch's rounds of workgroups,
+ * K5 and K1 on one stream: profiles/AB_LOG.md.) */
 afs_status afs_create(afs_ctx **ctx, const afs_config *cfg);
 void afs_destroy(afs_ctx *ctx);
 const char *afs_last_error(const afs_ctx *ctx);

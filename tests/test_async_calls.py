@@ -1,4 +1,4 @@
-"""Large tree calls without host read-backs (afs_capi.cpp shape_order, run_chunks): the slot order is
+"""Large tree calls without host read-backs (afs_capi.cpp shape_order, run_hop_call): the slot order is
 sorted on the device, and K5's compact mixed-hop slots are sized up front, the synthesis launches
 guarded on the device by the count K5 claimed.  Two AFS_ASYNC calls of 8192 utterances are queued
 back to back on one stream:

@@ -11,7 +11,7 @@ library device memory at any alignment.  Checked here:
     the launch-local sample index and copied back after an odd launch, tree_kernel.h tree_pair_run)
     bit for bit against the one-wave kernel, which has no second buffer;
   * K1's 128-byte output window and the section-25 pressure rows laid out congruent to it
-    (afs_capi.cpp run_chunks) with device output at every kind of alignment: the same audio as
+    (afs_capi.cpp p25_for) with device output at every kind of alignment: the same audio as
     into a host buffer, and the memory on both sides of the rows untouched.
 Bounds: GOLD_TOL against the oracle (every sequence stays under the 2048 samples it is defined
 for); bit for bit wherever two GPU paths are designed to be identical.

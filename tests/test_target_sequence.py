@@ -212,6 +212,28 @@ def test_gpu_target_sequence_equals_frames_path(oracle):
 
 
 @pytest.mark.gpu
+def test_gpu_shared_trajectories_16_lanes_equal_single_calls():
+    """The slot order of shared trajectories (afs_xcd_order.h) in the 16-lane kernel, eight utterances
+    per block: 21 utterances over 3 VCV sequences, interleaved, are three blocks (the last partly
+    padding) with every row split across blocks.  Each utterance's audio and rand() draw count equal,
+    bit for bit, a call of its own with its targets and seed."""
+    from areafunctionsynthesis_amd.synthesizer import Context
+    ctx = Context(22050.0, lanes=16)
+    shapes = np.concatenate([_vcv("a:", "b"), _vcv("i:", "g"), _vcv("u:", "d")])
+    B = 21
+    targets = np.array([[4 * (u % 3) + j for j in range(4)] for u in range(B)], dtype=np.int32)
+    seeds = np.arange(1, B + 1, dtype=np.uint32)
+    y = ctx.play_target_sequences(shapes, targets, SHORT, seeds=seeds).copy()
+    draws = ctx.rng_draws(B)
+    assert y.shape == (B, ctx.target_sequence_samples(SHORT)) and np.abs(y).max() > 1e-4
+    for u in range(B):
+        y1 = ctx.play_target_sequences(shapes, targets[u:u + 1], SHORT, seeds=seeds[u:u + 1])
+        assert np.array_equal(y[u], y1[0]), u
+        assert draws[u] == ctx.rng_draws(1)[0], u
+    ctx.close()
+
+
+@pytest.mark.gpu
 def test_gpu_target_sequence_errors():
     from areafunctionsynthesis_amd._native import AfsError
     from areafunctionsynthesis_amd.synthesizer import Context

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def write(path):
     from areafunctionsynthesis_amd import workloads
+    from areafunctionsynthesis_amd.params import default_shapes
     from areafunctionsynthesis_amd.synthesizer import Context, Synthesizer as Session
     out = {}
     for fs in (44100.0, 22050.0):
@@ -30,6 +31,16 @@ def write(path):
                   for k in range(frames.shape[1])]
             out[f"{name}_{fs:g}_session"] = np.concatenate([y for y in ys if y is not None and y.size], axis=1)
             s.close()
+        # shared trajectories: 21 utterances over 3 VCV sequences, interleaved (at 16 lanes three blocks,
+        # the last partly padding, every row split across blocks)
+        sh = default_shapes()
+        shapes = np.concatenate([np.stack([sh[v], sh[f"({v[0]}){c}({v[0]}):"], sh[v], sh[v]])
+                                 for v, c in (("a:", "b"), ("i:", "g"), ("u:", "d"))])
+        targets = np.array([[4 * (u % 3) + j for j in range(4)] for u in range(21)], dtype=np.int32)
+        timing = {"stationary_s": [0.02, 0.01, 0.02, 0.01], "transition_s": [0.01, 0.01, 0.01]}
+        out[f"targets_{fs:g}"] = ctx.play_target_sequences(shapes, targets, timing,
+                                                           seeds=np.arange(1, 22, dtype=np.uint32))
+        out[f"targets_{fs:g}_draws"] = ctx.rng_draws(21)
         ctx.close()
     np.savez(path, **out)
 
