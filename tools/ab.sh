@@ -3,6 +3,7 @@
 # (default "A B"), the phase profile of tools/phase_prof/libphase_prof_T.so (AB_PP=1) and a short
 # bench with areafunctionsynthesis_amd/libafs_T.so (AB_BATCH utterances, default 8192), alternating A B A B.  A tag "T+NAME=VALUE" runs
 # variant T with the environment variable NAME=VALUE (e.g. "stage+AFS_PLAN_BUDGET_MB=48000").
+# Both libraries of a tag come from `python -m areafunctionsynthesis_amd.build --tag T --profiler [flags]`.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out

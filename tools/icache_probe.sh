@@ -1,6 +1,7 @@
 #!/bin/bash
 # Instruction-cache counters of a bench step for A/B library builds (development tool, GPU box):
-# one rocprofv3 counter pass per tag T in $AB (areafunctionsynthesis_amd/libafs_T.so), each
+# one rocprofv3 counter pass per tag T in $AB (areafunctionsynthesis_amd/libafs_T.so, built by
+# python -m areafunctionsynthesis_amd.build --tag T), each
 # under its own time limit; summarised per kernel by tools/icache_summary.py.
 # usage: tools/icache_probe.sh TAG       outputs under gpurun_out/TAG/
 set -u

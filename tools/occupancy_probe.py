@@ -6,19 +6,20 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from areafunctionsynthesis_amd.build import COMMON, TREE_FLAGS  # noqa: E402
+from areafunctionsynthesis_amd.build import compile_command  # noqa: E402
 
 FIELDS = ("VGPRs", "AGPRs", "VGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
 
 
 def probe(w: int, waves: int):
-    cmd = (["/opt/rocm/bin/hipcc", "-c", "-x", "hip", os.path.join(ROOT, "areafunctionsynthesis_amd", "csrc", "tds_tree.hip"),
-            "-o", "/tmp/occ_probe.o", "--offload-arch=gfx950"] + COMMON + TREE_FLAGS +
-           [f"-DAFS_TREE_W={w}", f"-DAFS_TREE_MIN_WAVES={waves}", "-Rpass-analysis=kernel-resource-usage"])
-    txt = subprocess.run(cmd, capture_output=True, text=True).stderr
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = compile_command("tds_tree.hip", [f"-DAFS_TREE_W={w}", f"-DAFS_TREE_MIN_WAVES={waves}",
+                                               "-Rpass-analysis=kernel-resource-usage"], tmp)
+        txt = subprocess.run(cmd, capture_output=True, text=True).stderr
     out, cur = {}, None
     for line in txt.splitlines():
         m = re.search(r"Function Name: (\S+)", line)

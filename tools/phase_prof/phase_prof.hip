@@ -1,6 +1,7 @@
 // phase_prof.hip -- development tool: the tree kernel body with per-phase cycle counters
-// (s_memtime deltas, accumulated per wave).  Not part of libafs; built by this directory's
-// Makefile and driven by run.py on the GPU box.
+// (s_memtime deltas, accumulated per wave).  Not part of libafs; built with the tree kernel's
+// flags and linked with the library's objects by `python -m areafunctionsynthesis_amd.build
+// --profiler`, and driven by run.py on the GPU box.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>

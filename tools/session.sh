@@ -10,7 +10,7 @@
 #   pmc     FETCH_SIZE and WRITE_SIZE passes (one rocprofv3 run each) of one bench step
 #   sq      SQ fp64 pass (tools/pmc_sq_fp64.py summarises it)  mix    three SQ instruction-mix passes
 #   calib   the FETCH_SIZE calibration probe                    pp     per-phase cycle profile (tools/phase_prof)
-#   ab      alternated A/B of in-tree variants (AB="tagA tagB", tools/ab.sh; built by tools/build_variant.sh)
+#   ab      alternated A/B of in-tree variants (AB="tagA tagB", tools/ab.sh; built by python -m areafunctionsynthesis_amd.build --tag)
 # BENCH_ARGS: extra bench.py arguments for bench / prof / pmc / sq / mix (e.g. "--workload vcv").
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
