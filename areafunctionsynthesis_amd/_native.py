@@ -27,6 +27,9 @@ AFS_PROFILE = 0x2
 AFS_LANES_16 = 0x4
 AFS_LANES_64 = 0x8
 AFS_COMM_ID_BYTES = 128
+AFS_MAX_TAPS = 8  # afs.h
+AFS_TAP_PRESSURE = 0
+AFS_TAP_CURRENT = 1
 
 # Every symbol include/afs.h declares.
 EXPORTED = (
@@ -38,6 +41,7 @@ EXPORTED = (
     "afs_kernel_times_ex",
     "afs_shard_range", "afs_comm_unique_id", "afs_comm_create", "afs_comm_create_all", "afs_comm_destroy",
     "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times", "afs_multi_synthesize",
+    "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps", "afs_section_currents",
 )
 
 
@@ -64,6 +68,10 @@ class AfsConfig(ctypes.Structure):
 class AfsReport(ctypes.Structure):
     _fields_ = [("device_ms", ctypes.c_double), ("samples", ctypes.c_int64),
                 ("nonfinite_utterances", ctypes.c_int32), ("kernel", ctypes.c_int32)]
+
+
+class AfsTap(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32)]
 
 
 class AfsKernelTiming(ctypes.Structure):
@@ -144,12 +152,19 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_comm_gather_times.argtypes = [vp, dp, i32p]
     lib.afs_multi_synthesize.argtypes = [vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_int32, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_set_taps.argtypes = [vp, ctypes.POINTER(AfsTap), ctypes.c_int32]
+    lib.afs_synthesize_taps.argtypes = [vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp,
+                                        ctypes.POINTER(AfsReport)]
+    lib.afs_session_synthesize_taps.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(AfsReport)]
+    lib.afs_section_currents.argtypes = [ctypes.c_int32, i32p, i32p]
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",
                  "afs_to_int16", "afs_play_target_sequences", "afs_rng_draws", "afs_session_rng_draws", "afs_plan_hop_words",
                  "afs_kernel_times", "afs_kernel_times_ex", "afs_comm_unique_id", "afs_comm_create", "afs_comm_create_all",
                  "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times",
-                 "afs_multi_synthesize"):
+                 "afs_multi_synthesize", "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps",
+                 "afs_section_currents"):
         getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

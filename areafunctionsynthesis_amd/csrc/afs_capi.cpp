@@ -154,7 +154,23 @@ struct SynthCall {
   int B, width;
   const int32_t *frame_row;
   SlotOrder so;
+  // the _taps calls: tap k of utterance u to taps[(u * n_taps + k) * tstride + s] (null: no taps)
+  double *taps = nullptr;
+  int64_t tstride = 0;
 };
+
+// the context's tap list as K1 reads it: a current from the slot the solver leaves it in, a
+// pressure from the slot its owner publishes it into (afs_model.h TapSet)
+afs::TapSet tap_set(const afs_ctx *c) {
+  afs::TapSet t;
+  t.n = c->n_taps;
+  for (int k = 0; k < c->n_taps; ++k) {
+    const bool cur = c->taps[k].kind == AFS_TAP_CURRENT;
+    t.sec[k] = cur ? -1 : c->taps[k].index;
+    t.x[k] = cur ? c->host_tab.tap_u[c->taps[k].index] : c->host_tab.tap_p + k;
+  }
+  return t;
+}
 
 // The noise-source plans one K1 launch reads: the dense records, the hop records (hop mode; K1
 // indexes them from the launch's first hop), and for the guarded launches of run_hop_call K5's count
@@ -203,6 +219,11 @@ afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, in
     const int64_t blocks = so.grid > 0 ? so.grid : ((int64_t)call.B + afs::TREE_UPB - 1) / afs::TREE_UPB;
     const int64_t slots = std::max<int64_t>(1, c->simds / 2), rounds = (blocks + slots - 1) / slots;
     a.stat_prio = (call.width == afs::TREE_W && rounds >= 2) ? 2 : 0;
+  }
+  if (call.taps) {  // (every launch of the call carries the list: the rows go on where the last launch stopped)
+    a.taps = tap_set(c);
+    a.tap_out = call.taps + s0;
+    a.tap_stride = call.tstride;
   }
   hipEvent_t e1 = prof_event(c);
   HIP_TRY(c, afs::launch_tree_synth(a, call.width, c->stream));
@@ -664,14 +685,26 @@ static afs_status shape_order(afs_ctx *c, const afs_frame *dframes, int64_t fstr
   return AFS_OK;
 }
 
-// afs_synthesize; force_async: leave the stream running unless a host buffer needs a wait
+// what a _taps call needs beside the plain call's arguments
+static afs_status taps_check(afs_ctx *c, const char *fn, const double *taps_out) {
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
+  if (!taps_out) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: taps_out is NULL", fn);
+  return AFS_OK;
+}
+
+// afs_synthesize; force_async: leave the stream running unless a host buffer needs a wait;
+// taps_out: afs_synthesize_taps (the context's taps beside the audio), else null
 static afs_status synth_core(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
                              int32_t hop, double *out, uint8_t *nonfinite, afs_report *rep, bool force_async,
-                             int lanes = 0) {
+                             int lanes = 0, double *taps_out = nullptr) {
   if (!frames || !out || B <= 0 || F < 2 || hop < 1)
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int64_t T = (int64_t)(F - 1) * hop;
+  double *dtaps = nullptr;
+  bool host_taps = false;
+  const size_t taps_bytes = (size_t)B * (size_t)c->n_taps * (size_t)T * sizeof(double);
   afs_status s;
   const afs_frame *dframes;
   const uint32_t *dseeds;
@@ -683,10 +716,18 @@ static afs_status synth_core(afs_ctx *c, const afs_frame *frames, const uint32_t
   const int width = lanes > 0 ? lanes : lanes_for(c, B);
   if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  if (taps_out && (s = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps,
+                                       &host_taps)) != AFS_OK)
+    return s;
   SynthCall call{dframes, F, B, F - 1, hop, dout, T, c->ws, c->rng, c->tree_lanes, pad64(B), B, width, nullptr, {}};
+  call.taps = dtaps;
+  call.tstride = T;
   if ((s = shape_order(c, dframes, F, B, width, &call.so)) != AFS_OK) return s;
   if ((s = run_call(c, call)) != AFS_OK) return s;
-  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, force_async || (c->cfg.flags & AFS_ASYNC));
+  // (a host taps_out is copied back as a host out is, and the call then waits)
+  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
+  const bool async = (force_async || (c->cfg.flags & AFS_ASYNC)) && !host_taps;
+  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, async);
 }
 
 afs_status afs::synthesize_async(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
@@ -704,6 +745,34 @@ afs_status afs_synthesize(afs_ctx *c, const afs_frame *frames, const uint32_t *s
   if (!frames || !out || B <= 0 || F < 2 || hop < 1)
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
   return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, rep, false);
+}
+
+afs_status afs_set_taps(afs_ctx *c, const afs_tap *taps, int32_t n) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "afs_set_taps: tree solver only");
+  if (n < 0 || n > AFS_MAX_TAPS || (n > 0 && !taps))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_set_taps: need 0 <= n <= %d taps", AFS_MAX_TAPS);
+  for (int k = 0; k < n; ++k) {
+    const int lim = taps[k].kind == AFS_TAP_PRESSURE ? afs::NS : taps[k].kind == AFS_TAP_CURRENT ? afs::NC : 0;
+    if (taps[k].index < 0 || taps[k].index >= lim)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_set_taps: tap %d: kind %d, index %d", k, taps[k].kind, taps[k].index);
+  }
+  for (int k = 0; k < n; ++k) c->taps[k] = taps[k];
+  c->n_taps = n;
+  return AFS_OK;
+}
+
+afs_status afs_synthesize_taps(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
+                               int32_t hop, double *out, double *taps_out, uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  const afs_status s = taps_check(c, "afs_synthesize_taps", taps_out);
+  if (s != AFS_OK) return s;
+  return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, rep, false, 0, taps_out);
+}
+
+afs_status afs_section_currents(int32_t section, int32_t *in, int32_t out[2]) {
+  if (!in || !out || !afs::section_currents(section, in, out)) return AFS_ERR_INVALID_ARGUMENT;
+  return AFS_OK;
 }
 
 int32_t afs_lanes_per_utterance(const afs_ctx *c, int32_t batch) {
@@ -928,8 +997,11 @@ void afs_session_destroy(afs_session *s) {
   delete s;
 }
 
-afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32_t n, double *out,
-                                  uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+}  // extern "C"
+
+// afs_session_synthesize; taps_out: afs_session_synthesize_taps, else null
+static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t n, double *out, double *taps_out,
+                               uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
   if (!s || !frames) return AFS_ERR_INVALID_ARGUMENT;
   afs_ctx *c = s->ctx;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -970,9 +1042,17 @@ afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32
       s->hout_cap = nout;
     }
   }
+  double *dtaps = nullptr;
+  bool host_taps = false;
+  const size_t taps_bytes = nout * (size_t)c->n_taps * sizeof(double);
+  if (taps_out && (st = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps,
+                                        &host_taps)) != AFS_OK)
+    return st;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  const SynthCall call{s->pair, 2, B, 1, n, dout, n, s->ws, s->rng, s->tree_lanes, s->bp, B, s->lanes, nullptr,
-                       plain_order(c)};
+  SynthCall call{s->pair, 2, B, 1, n, dout, n, s->ws, s->rng, s->tree_lanes, s->bp, B, s->lanes, nullptr,
+                 plain_order(c)};
+  call.taps = dtaps;
+  call.tstride = n;
   if ((st = run_call(c, call)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   // prevTube = *newTube (Synthesizer.cpp:633-637)
@@ -981,10 +1061,27 @@ afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32
   bool nf_sync = false;
   if ((st = nonfinite_report(c, s->ws, s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
   if (host_out) HIP_TRY(c, hipMemcpyAsync(s->hout, dout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a session call always waits: its audio is due now)
   if (host_out) std::memcpy(out, s->hout, nout * sizeof(double));
   if (produced) *produced = n;
   return fill_report(c, rep, (int64_t)B * n);
+}
+
+extern "C" {
+
+afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32_t n, double *out,
+                                  uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+  return session_core(s, frames, n, out, nullptr, nonfinite, produced, rep);
+}
+
+// (the latching first call produces no samples and leaves taps_out alone, as it leaves out)
+afs_status afs_session_synthesize_taps(afs_session *s, const afs_frame *frames, int32_t n, double *out,
+                                       double *taps_out, uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  const afs_status st = taps_check(s->ctx, "afs_session_synthesize_taps", taps_out);
+  if (st != AFS_OK) return st;
+  return session_core(s, frames, n, out, taps_out, nonfinite, produced, rep);
 }
 
 afs_status afs_session_rng_draws(afs_session *s, int64_t *draws) {

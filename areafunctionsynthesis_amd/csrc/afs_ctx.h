@@ -64,6 +64,11 @@ struct afs_ctx {
   // (device 0) the gathered int16 audio of the whole batch
   void *m_out = nullptr, *m_pcm = nullptr, *m_nf = nullptr, *m_root = nullptr;
   size_t m_out_bytes = 0, m_pcm_bytes = 0, m_nf_bytes = 0, m_root_bytes = 0;
+  // signal taps (afs_set_taps): the list the _taps calls collect, and the staging of a host taps_out
+  afs_tap taps[AFS_MAX_TAPS] = {};
+  int32_t n_taps = 0;
+  void *stage_taps = nullptr;
+  size_t stage_taps_bytes = 0;
   int32_t last_B = 0;        // batch of the last whole-trajectory call (afs_rng_draws)
   int32_t *dcount = nullptr;
   int32_t *hcount = nullptr;  // pinned host copy of dcount

@@ -241,6 +241,21 @@ struct Tables {
   Uni uni;
 
   afs_options opt;
+  // signal taps (afs.h afs_set_taps): the double of the tree kernel's LDS block that holds branch
+  // current c (the reference's numbering) once the sample's solve is done, and the first of the
+  // AFS_MAX_TAPS doubles the tapped pressures are published into (tree_core.h X_TAP)
+  int16_t tap_u[NC];
+  int16_t tap_p;
+};
+
+// The taps of a tree-kernel launch (a kernel argument: scalar registers).  Tap k is read from
+// double x[k] of the utterance's LDS block after the sample's last barrier: a current's own slot
+// (Tables::tap_u), or the slot its owner publishes the pressure of section sec[k] into
+// (tree_core.h X_TAP + k; sec[k] < 0: a current, nothing to publish).
+struct TapSet {
+  int32_t n = 0;
+  int32_t sec[AFS_MAX_TAPS] = {};
+  int32_t x[AFS_MAX_TAPS] = {};
 };
 
 // TdsModel's default options (TdsModel.cpp:35-44).
@@ -261,6 +276,9 @@ inline afs_options default_options() {
 
 // Host: build the tables for a sampling rate and option set (afs_tables.cpp).
 void build_tables(Tables *t, double fs_hz, const afs_options &opt);
+// Host: the currents into and out of a section (Tables::cin, cout0, cout1; -1: none); false for a
+// section outside 0 .. NS - 1.
+bool section_currents(int section, int32_t *in, int32_t out[2]);
 // Host: IirFilter::createChebyshev restatement used for the output filter.
 int chebyshev(double ratio, bool highpass, int poles, double *a, double *b);
 

@@ -620,6 +620,11 @@ void build_tables(Tables *t, double fs_hz, const afs_options &opt) {
     for (int k = 0; k < 6; ++k) q.x_rad[k] = (uint16_t)(q.x_rad[k] * 8);
   }
   bank_edge_slots(c);
+  // Signal taps: the solver leaves current c's new value at X_U + c for every c (the arm records
+  // address the nodes by the reference's current numbers, the leaves 93-96 included), the update
+  // phase reads it there and nothing writes X_U again before the next sample's solve.
+  for (int cur = 0; cur < NC; ++cur) t->tap_u[cur] = (int16_t)(X_U + cur);
+  t->tap_p = (int16_t)X_TAP;
   for (int k = 0; k < NSTATIC; ++k) {
     int s = k < 23 ? k : k + 46;
     c.stat[k][ST_E] = t->E[s];
@@ -630,6 +635,19 @@ void build_tables(Tables *t, double fs_hz, const afs_options &opt) {
     c.stat[k][ST_L] = t->L[s];
     c.stat[k][ST_R] = t->R[s];
   }
+}
+
+bool section_currents(int section, int32_t *in, int32_t out[2]) {
+  if (section < 0 || section >= NS) return false;
+  static const Tables *topo = [] {
+    Tables *t = new Tables();
+    topology(t);
+    return t;
+  }();
+  *in = topo->cin[section];
+  out[0] = topo->cout0[section];
+  out[1] = topo->cout1[section];
+  return true;
 }
 
 }  // namespace afs

@@ -57,6 +57,12 @@ struct TreeArgs {
   // phase group and the solver, 3 the whole launch (afs_capi.cpp launch_synth_output: 2 from two
   // rounds of workgroups per CU slot, 0 below; profiles/r06_pair_ab.txt r06zh-r06zm)
   int stat_prio = 0;
+  // signal taps (afs.h afs_set_taps; taps.n > 0 launches the kernels' TAPS forms, which always run the
+  // full noise phases): tap k of utterance u goes to tap_out[(u * taps.n + k) * tap_stride + s - s_begin]
+  // -- rows by utterance, whatever slot the order gives it
+  TapSet taps{};
+  double *tap_out = nullptr;
+  int64_t tap_stride = 0;
 };
 // K5: the noise-source plans of samples [s_begin, s_end) of `rows` frame rows.
 struct PlanArgs {

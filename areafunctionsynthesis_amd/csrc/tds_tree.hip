@@ -11,27 +11,28 @@ namespace {
 
 // one kernel per glottis model (TriangularGlottis, the reference's; TwoMassModel), plan mode
 // (HOPS: hop records, hops >= PLAN_HOP_MIN; dense records otherwise) and lanes per utterance W
-// (16: the throughput kernel; 64: the voice kernel, tree_kernel.h)
-template <int MODEL, bool HOPS, int W>
+// (16: the throughput kernel; 64: the voice kernel, tree_kernel.h); TAPS: the form a launch with
+// signal taps runs (TreeArgs::taps) -- the tap-less kernels hold none of its code
+template <int MODEL, bool HOPS, int W, bool TAPS = false>
 __global__ void __launch_bounds__(64 * Geom<W>::WPB, AFS_TREE_MIN_WAVES) tree_synth_kernel(TreeArgs a) {
   __shared__ WaveLdsT<W> lds;
-  tree_synth_body<false, MODEL, HOPS, W>(a, lds, nullptr);
+  tree_synth_body<false, MODEL, HOPS, W, TAPS>(a, lds, nullptr);
 }
 
 #if AFS_PAIR
 // the wave-pair build of the throughput kernel (tree_kernel.h tree_pair_body): four waves per
 // workgroup, two per SIMD
-template <int MODEL, bool HOPS>
+template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(256, 2) tree_pair_kernel(TreeArgs a) {
   __shared__ WaveLdsT<TW> lds;
   __shared__ int pattern[5];
-  tree_pair_body<MODEL, HOPS>(a, lds, pattern);
+  tree_pair_body<MODEL, HOPS, false, TAPS>(a, lds, pattern);
 }
 // the voice kernel's pairs: two waves per utterance, each may take a whole SIMD's registers
-template <int MODEL, bool HOPS>
+template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(128, 2) tree_pair64_kernel(TreeArgs a) {
   __shared__ WaveLdsT<64> lds;
-  tree_pair64_body<MODEL, HOPS>(a, lds);
+  tree_pair64_body<MODEL, HOPS, false, TAPS>(a, lds);
 }
 #endif
 
@@ -156,57 +157,55 @@ hipError_t launch_tree_reset(void *lane_state, double *lds_state, int B, const u
   return hipGetLastError();
 }
 
-// the one-wave kernel (every phase on one wave)
-template <int W>
-static void launch_one_wave(const TreeArgs &a, dim3 grid, dim3 block, bool two, hipStream_t st) {
+// One launch per (glottis model, plan mode): K<MODEL, HOPS>() names the kernel.
+template <class K>
+static void launch_model_hops(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st, K kernel) {
+  const bool two = a.uni.opt.glottis_model == AFS_GLOTTIS_TWO_MASS;
   if (a.hops) {
-    if (two) hipLaunchKernelGGL((tree_synth_kernel<AFS_GLOTTIS_TWO_MASS, true, W>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((tree_synth_kernel<AFS_GLOTTIS_TRIANGULAR, true, W>), grid, block, 0, st, a);
+    if (two) hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TWO_MASS>{}, std::true_type{}), grid, block, 0, st, a);
+    else hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TRIANGULAR>{}, std::true_type{}), grid, block, 0, st, a);
   } else {
-    if (two) hipLaunchKernelGGL((tree_synth_kernel<AFS_GLOTTIS_TWO_MASS, false, W>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((tree_synth_kernel<AFS_GLOTTIS_TRIANGULAR, false, W>), grid, block, 0, st, a);
+    if (two) hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TWO_MASS>{}, std::false_type{}), grid, block, 0, st, a);
+    else hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TRIANGULAR>{}, std::false_type{}), grid, block, 0, st, a);
   }
 }
 
-template <int W>
+// the one-wave kernel (every phase on one wave)
+template <int W, bool TAPS>
+static void launch_one_wave(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st) {
+  launch_model_hops(a, grid, block, st, [](auto m, auto h) { return tree_synth_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>; });
+}
+
+template <int W, bool TAPS>
 static void launch_synth_w(const TreeArgs &a, hipStream_t st) {
   constexpr int UPB_ = Geom<W>::UPB;
   const dim3 grid(a.grid_blocks > 0 ? a.grid_blocks : (a.B + UPB_ - 1) / UPB_), block(64 * Geom<W>::WPB);
-  const bool two = a.uni.opt.glottis_model == AFS_GLOTTIS_TWO_MASS;
 #if AFS_PAIR
   if constexpr (W == TW) {  // (the one-wave kernel at 16 lanes is not instantiated in this build)
     static_assert(Geom<TW>::WPB == 2, "a wave pair per four utterances: 4 waves per 8-utterance block");
-    const dim3 pblock(256);
-    if (a.hops) {
-      if (two) hipLaunchKernelGGL((tree_pair_kernel<AFS_GLOTTIS_TWO_MASS, true>), grid, pblock, 0, st, a);
-      else hipLaunchKernelGGL((tree_pair_kernel<AFS_GLOTTIS_TRIANGULAR, true>), grid, pblock, 0, st, a);
-    } else {
-      if (two) hipLaunchKernelGGL((tree_pair_kernel<AFS_GLOTTIS_TWO_MASS, false>), grid, pblock, 0, st, a);
-      else hipLaunchKernelGGL((tree_pair_kernel<AFS_GLOTTIS_TRIANGULAR, false>), grid, pblock, 0, st, a);
-    }
+    launch_model_hops(a, grid, dim3(256), st, [](auto m, auto h) { return tree_pair_kernel<decltype(m)::value, decltype(h)::value, TAPS>; });
   } else if constexpr (W == 64) {
     if (a.B <= TREE_PAIR64_MAX) {
-      const dim3 pblock(128);
-      if (a.hops) {
-        if (two) hipLaunchKernelGGL((tree_pair64_kernel<AFS_GLOTTIS_TWO_MASS, true>), grid, pblock, 0, st, a);
-        else hipLaunchKernelGGL((tree_pair64_kernel<AFS_GLOTTIS_TRIANGULAR, true>), grid, pblock, 0, st, a);
-      } else {
-        if (two) hipLaunchKernelGGL((tree_pair64_kernel<AFS_GLOTTIS_TWO_MASS, false>), grid, pblock, 0, st, a);
-        else hipLaunchKernelGGL((tree_pair64_kernel<AFS_GLOTTIS_TRIANGULAR, false>), grid, pblock, 0, st, a);
-      }
+      launch_model_hops(a, grid, dim3(128), st, [](auto m, auto h) { return tree_pair64_kernel<decltype(m)::value, decltype(h)::value, TAPS>; });
       return;
     }
   }
-  if constexpr (W != TW) launch_one_wave<W>(a, grid, block, two, st);
+  if constexpr (W != TW) launch_one_wave<W, TAPS>(a, grid, block, st);
 #else
-  launch_one_wave<W>(a, grid, block, two, st);
+  launch_one_wave<W, TAPS>(a, grid, block, st);
 #endif
 }
 
 hipError_t launch_tree_synth(const TreeArgs &a, int lanes, hipStream_t st) {
   if (a.B <= 0 || a.s_end <= a.s_begin) return hipSuccess;
-  if (lanes == 64) launch_synth_w<64>(a, st);
-  else launch_synth_w<TW>(a, st);
+  if (a.taps.n > 0) {
+    if (a.taps.n > AFS_MAX_TAPS || !a.tap_out) return hipErrorInvalidValue;
+    if (lanes == 64) launch_synth_w<64, true>(a, st);
+    else launch_synth_w<TW, true>(a, st);
+  } else {
+    if (lanes == 64) launch_synth_w<64, false>(a, st);
+    else launch_synth_w<TW, false>(a, st);
+  }
   return hipGetLastError();
 }
 

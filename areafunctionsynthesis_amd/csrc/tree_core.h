@@ -112,6 +112,11 @@ enum : int {
   X_STRIDE = X_TOTAL + ((16 - X_TOTAL % 32) + 32) % 32
 };
 static_assert(X_STRIDE % 32 == 16, "utterance blocks offset by half a bank row");
+// Signal taps (afs.h afs_set_taps): the pressure of tap k is published into the stride's padding
+// behind the saved image -- LDS the blocks already take, outside what a launch saves and restores
+// (a tap's value is read in the sample that wrote it).
+constexpr int X_TAP = X_TOTAL;
+static_assert(X_TAP + AFS_MAX_TAPS <= X_STRIDE, "the taps' slots fit the padding between the utterance blocks");
 
 // Phase ids for Exec::mark (cycle accounting in tools/phase_prof; a no-op otherwise).
 enum : int {
@@ -2114,6 +2119,30 @@ AFS_HD inline double section_pressure(const double *X, const Consts &C, int s) {
   return X[X_D + s] + X[X_E + s - DYN0] * net;
 }
 
+// Signal taps: after phase_update, the lane that owns a tapped section publishes its new pressure
+// into the tap's slot.  An unrolled walk over the role's slots selects the value (the slots are
+// registers: no dynamic index); a lane that owns none of the section stores nothing.  The currents
+// need no publishing: they are read where the solver left them (TapSet::x).
+template <int W, int ROLE = ROLE_ALL>
+AFS_HD inline void tap_publish(int gl, const Lane<W> &R, double *X, const TapSet &tp) {
+  using S = Shape<W>;
+#pragma unroll
+  for (int k = 0; k < AFS_MAX_TAPS; ++k) {
+    if (k < tp.n && tp.sec[k] >= 0) {
+      double v = 0.0;
+      bool own = false;
+#pragma unroll
+      for (int j = 0; j < S::NSL; ++j) {
+        if (!role_slot<ROLE>(j, S::ND)) continue;
+        const bool hit = slot_section<W>(j, gl) == tp.sec[k];
+        v = hit ? R.p[j] : v;
+        own |= hit;
+      }
+      if (own) X[X_TAP + k] = v;
+    }
+  }
+}
+
 // The output stage after the radiated flow (Synthesizer.cpp:614-627): dU/dt, the 8-pole
 // Chebyshev low-pass, x 0.004 / 32767.  It does not feed back into the tube, so it can run
 // over a whole hop of flows afterwards (output_filter_run) or per sample (output_filter_one);
@@ -2423,8 +2452,9 @@ AFS_HD inline void rng_ring_pos_store(Xc &x, double *X) {
     }
   });
 }
-template <int W, int MODEL, int NZ, int ROLE, bool VARLOSS, class Xc>
-AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par) {
+template <int W, int MODEL, int NZ, int ROLE, bool VARLOSS, bool TAPS = false, class Xc>
+AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par,
+                                      const TapSet *taps = nullptr) {
   static_assert(ROLE == ROLE_DYN || ROLE == ROLE_STAT, "a wave pair's roles");
   constexpr bool STAT = ROLE == ROLE_STAT;
   AFS_SCHED_BARRIER();
@@ -2496,14 +2526,20 @@ AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Cons
                   [&](Lane<W> &R) { R.sample = phase_output_flow(X); });
   else
     x.par([&](int gl, Lane<W> &R) { phase_update<W, ROLE>(gl, R, X, X, U, C); });
+  // (TAPS: each role publishes the tapped pressures it owns before P4's barrier; the DYN wave reads
+  // them after it, and no wave writes them again before the next sample's three barriers)
+  if constexpr (TAPS) x.par([&](int gl, Lane<W> &R) { tap_publish<W, ROLE>(gl, R, X, *taps); });
   x.mark(PH_UPDATE);
   x.bar();
   x.mark(PH_P4WAIT);
 }
-template <int W, int MODEL, int NZ, int ROLE, class Xc>
-AFS_HD inline void sample_step_pair(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par) {
-  if (U.opt.glottis_loss == AFS_ENTRANCE_LOSS_VARIABLE) sample_step_pair_v<W, MODEL, NZ, ROLE, true>(x, X, U, C, ratio, par);
-  else sample_step_pair_v<W, MODEL, NZ, ROLE, false>(x, X, U, C, ratio, par);
+template <int W, int MODEL, int NZ, int ROLE, bool TAPS = false, class Xc>
+AFS_HD inline void sample_step_pair(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par,
+                                    const TapSet *taps = nullptr) {
+  if (U.opt.glottis_loss == AFS_ENTRANCE_LOSS_VARIABLE)
+    sample_step_pair_v<W, MODEL, NZ, ROLE, true, TAPS>(x, X, U, C, ratio, par, taps);
+  else
+    sample_step_pair_v<W, MODEL, NZ, ROLE, false, TAPS>(x, X, U, C, ratio, par, taps);
 }
 
 }  // namespace tree

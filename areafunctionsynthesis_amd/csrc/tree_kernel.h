@@ -15,6 +15,8 @@
 // incremental sessions continue exactly where they stopped.
 #pragma once
 
+#include <type_traits>
+
 #include <hip/hip_runtime.h>
 
 #include "afs_tree.h"
@@ -265,11 +267,44 @@ __device__ __forceinline__ int noise_variant(const TreeArgs &a, int g = -1, int 
   return __builtin_amdgcn_readfirstlane(on ? nz : (int)NZ_FULL);
 }
 
+// Signal taps (TAPS kernels; afs.h afs_set_taps), after the sample's last barrier: every lane of the
+// collecting wave reads tap k's value from the utterance's LDS block (one address per utterance: a
+// broadcast read) and keeps it if the sample's position in tap row k's 128-byte line is the lane's own
+// -- a register window per tap, as wo / wp hold the audio's -- and lanes 0-15 store the window as one
+// whole line when its last sample is in or the launch ends.  Each row is aligned on its own address
+// (rows are T doubles apart: any position in a line), a first or last partial line stores its own
+// lanes only, and nothing is written outside the row's n samples of this launch.
+struct TapWindow {
+  double w[AFS_MAX_TAPS] = {};
+  double *row0;  // tap 0's row of this lane's utterance, at the launch's first sample
+  int line0;     // its position in a 128-byte line
+  __device__ __forceinline__ TapWindow(const TreeArgs &a, int ue)
+      : row0(a.tap_out + (int64_t)ue * a.taps.n * a.tap_stride),
+        line0((int)((reinterpret_cast<uintptr_t>(row0) >> 3) & 15)) {}
+  __device__ __forceinline__ void collect(const TreeArgs &a, const double *X, int gl, bool valid, int64_t t, int64_t n) {
+    const int sl = (int)(a.tap_stride & 15);
+#pragma unroll
+    for (int k = 0; k < AFS_MAX_TAPS; ++k) {
+      if (k < a.taps.n) {
+        const double v = X[a.taps.x[k]];
+        const int j = (line0 + k * sl + (int)(t & 15)) & 15;  // the sample's position in row k's line
+        w[k] = gl == j ? v : w[k];
+        if (valid && (j == 15 || t + 1 == n) && gl <= j && t - j + gl >= 0) row0[k * a.tap_stride + t - j + gl] = w[k];
+      }
+    }
+  }
+};
+struct NoTapWindow {  // (kernels without TAPS: nothing to keep)
+  __device__ __forceinline__ NoTapWindow(const TreeArgs &, int) {}
+};
+template <bool TAPS> using TapWindowT = std::conditional_t<TAPS, TapWindow, NoTapWindow>;
+
 // prof (PROF only): per wave, PH_COUNT cycle sums (s_memtime) over the launch.
 // HOPS: the plan words come from hop records (a.hops, tree_plan.h PlanHop): lane gl keeps word
 // gl's kind and inputs for the hop and evaluates the word at every sample; a mixed hop's samples
 // read their dense records as without HOPS.
-template <bool PROF, int MODEL, bool HOPS, int W, int NZ>
+// TAPS: the launch's signal taps collected after each sample (TapWindow); no tap code otherwise.
+template <bool PROF, int MODEL, bool HOPS, int W, int NZ, bool TAPS = false>
 __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
   constexpr int UPB_ = Geom<W>::UPB, WPB_ = Geom<W>::WPB;
   const int lane = threadIdx.x;  // 0 .. 64 WPB - 1
@@ -337,6 +372,7 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
   // the window in LDS: +0.4 % / +0.5 % (profiles/r04f_store_ab.txt).
   const int o_line = (int)((reinterpret_cast<uintptr_t>(o) >> 3) & 15);
   double wo = 0.0, wp = 0.0;
+  TapWindowT<TAPS> tw(a, ue);
   const double dhop = (double)hop, inv_hop = 1.0 / dhop;
   ex.sync();
   uint64_t next = hmixed ? (HOPS ? pd[i * PLAN_WORDS] : pl[0]) : 0;
@@ -369,6 +405,11 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
         o[t - j + gl] = wo;
         p25o[t - j + gl] = wp;
       }
+    }
+    if constexpr (TAPS) {  // (the owners' pressures through LDS: a wave fence orders them before the reads)
+      tap_publish<W>(gl, R, X, a.taps);
+      ex.sync();
+      tw.collect(a, X, gl, valid, t, n);
     }
     if (++i == hop) {
       i = 0;
@@ -412,10 +453,14 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
 // different variants: each reaches the one __syncthreads of the table staging in its own copy.  One
 // body with the variant switched in the noise phase instead -- sample_step's NZ_DYN -- measured
 // -1.7 %, profiles/r05f_variant_order_ab.txt.)
-template <bool PROF, int MODEL, bool HOPS = false, int W = TW>
+// (TAPS: the full noise phases only -- the variants give the same values, and each would be one
+// more copy of the body to compile)
+template <bool PROF, int MODEL, bool HOPS = false, int W = TW, bool TAPS = false>
 __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
   if (!block_has_work<W>(a)) return;
-  if constexpr (HOPS) {
+  if constexpr (TAPS) {
+    tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL, true>(a, lds, prof);
+  } else if constexpr (HOPS) {
     with_noise_variant(noise_variant<W>(a), [&](auto V) {
       tree_synth_run<PROF, MODEL, HOPS, W, decltype(V)::value>(a, lds, prof);
     });
@@ -434,7 +479,7 @@ __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &
 // slots' state, so the pair's kernel must fit 256 registers per lane.
 // ---------------------------------------------------------------------------
 // (W = 64: the voice kernel's pairs, one utterance per workgroup of two waves, tree_pair64_body)
-template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW>
+template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW, bool TAPS = false>
 __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &lds, int grp, uint64_t *prof = nullptr) {
   constexpr int UPB_ = Geom<W>::UPB;
   constexpr int NT = 2 * 64 * Geom<W>::WPB;  // threads per workgroup (a pair per wave of the one-wave kernel)
@@ -486,6 +531,9 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
   NextFrame<W> nf{};
   const int o_line = (int)((reinterpret_cast<uintptr_t>(o) >> 3) & 15);
   double wo = 0.0, wp = 0.0;
+  // (TAPS: the DYN wave, which owns the output window, collects; the STAT wave's pressures reach it
+  // through LDS across P4's barrier, tree_core.h sample_step_pair_v)
+  TapWindowT<(TAPS && ROLE == ROLE_DYN)> tw(a, ue);
   const double dhop = (double)hop, inv_hop = 1.0 / dhop;
   if constexpr (ROLE == ROLE_STAT) {  // (the ring's head and pending count from the saved lane state)
     if (gl == 0) {
@@ -517,7 +565,8 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
     } else if constexpr (!HOPS) {
       if (i + 1 == hop && t + 1 < n) nf.load(gl, fu + k + 1);
     }
-    sample_step_pair<W, MODEL, NZ, ROLE>(ex, X, a.uni, C, ratio, (int)(t & 1));
+    sample_step_pair<W, MODEL, NZ, ROLE, TAPS>(ex, X, a.uni, C, ratio, (int)(t & 1), &a.taps);
+    if constexpr (TAPS && ROLE == ROLE_DYN) tw.collect(a, X, gl, valid, t, n);
     if constexpr (ROLE == ROLE_DYN) {
       const int j = (o_line + (int)t) & 15;
       const double p25v = GpuExec<false, W>::template dpp<0x152>(R.p[0]);
@@ -603,7 +652,7 @@ __device__ unsigned int pair_cu_slots[2048];
 // SIMD would share its issue slots.  When a workgroup's four waves do not sit on four SIMDs, by the
 // wave index.  Any placement gives a valid pairing; this only balances the SIMDs (against roles by
 // the wave index, the wave slot's or the block's parity: profiles/r06_pair_ab.txt).
-template <int MODEL, bool HOPS, bool PROF = false>
+template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false>
 __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &lds, int *pattern,
                                                uint64_t *prof = nullptr) {
   if (!block_has_work<TW>(a)) return;
@@ -638,7 +687,9 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
   }
   const bool stat = st != 0;
   if (!stat) {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF>(a, lds, grp, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, TW, TAPS>(a, lds, grp, prof);
+  } else if constexpr (TAPS) {  // (the full noise phases only: tree_synth_body)
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, TW, true>(a, lds, grp, prof);
   } else if constexpr (HOPS) {
     const int g = grp * Geom<TW>::UPW + ((int)threadIdx.x % 64) / TW, gl = (int)threadIdx.x % TW;
     with_noise_variant(noise_variant<TW>(a, g, gl), [&](auto V) {
@@ -653,12 +704,14 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
 // The voice kernel's pairs (64 lanes per utterance): one utterance per workgroup of two waves, wave 0
 // DYN and wave 1 STAT, for batches that leave a SIMD to each wave (afs_tree.h TREE_PAIR64_MAX): the
 // sample's chain split over two SIMDs instead of one wave's.
-template <int MODEL, bool HOPS, bool PROF = false>
+template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false>
 __device__ __forceinline__ void tree_pair64_body(const TreeArgs &a, WaveLdsT<64> &lds, uint64_t *prof = nullptr) {
   if (!block_has_work<64>(a)) return;
   const bool stat = threadIdx.x >= 64;
   if (!stat) {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, 64>(a, lds, 0, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, 64, TAPS>(a, lds, 0, prof);
+  } else if constexpr (TAPS) {
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64, true>(a, lds, 0, prof);
   } else if constexpr (HOPS) {
     with_noise_variant(noise_variant<64>(a, 0, (int)threadIdx.x % 64), [&](auto V) {
       tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF, 64>(a, lds, 0, prof);

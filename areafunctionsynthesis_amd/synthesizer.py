@@ -109,11 +109,25 @@ class Context:
     def synchronize(self) -> None:
         _native.check(self._lib.afs_synchronize(self._h), self._h, "afs_synchronize")
 
-    def synthesize(self, frames, hop: int, seeds=None, out=None, report: bool = False, nonfinite=None):
+    def set_taps(self, taps) -> None:
+        """The signal taps ``synthesize(..., taps=True)`` and ``synthesize_signal_tds(..., taps=True)``
+        return beside the audio (tree solver): up to AFS_MAX_TAPS entries, each a name of
+        :data:`TAPS`, ``("pressure", section)`` or ``("current", index)`` in the reference's
+        numbering.  An empty list clears them."""
+        taps = [tap(t) for t in taps]
+        arr = (_native.AfsTap * max(len(taps), 1))(*[_native.AfsTap(k, i) for k, i in taps])
+        _native.check(self._lib.afs_set_taps(self._h, arr, len(taps)), self._h, "afs_set_taps")
+        self.n_taps = len(taps)
+
+    def synthesize(self, frames, hop: int, seeds=None, out=None, report: bool = False, nonfinite=None,
+                   taps=False, taps_out=None):
         """frames[B, F] (FRAME_DTYPE array, or a uint8 torch tensor [B, F, 1072] on the GPU)
         -> audio[B, (F-1)*hop] float64.  ``seeds=None``: 1 .. B.  ``nonfinite``: optional uint8
         array / tensor of B flags (1 = the utterance's audio holds NaN/Inf); with ``report``
-        the returned dict carries them under ``nonfinite`` too."""
+        the returned dict carries them under ``nonfinite`` too.  ``taps=True``: returns
+        ``(audio, taps[B, n_taps, T])`` -- the taps of :meth:`set_taps` after every sample
+        (``taps_out``: a numpy array or GPU tensor to receive them) -- and with ``report``
+        ``(audio, taps, report)``."""
         if isinstance(frames, np.ndarray):
             if frames.dtype != FRAME_DTYPE or frames.ndim != 2:
                 raise ValueError("frames must be a 2-D FRAME_DTYPE array [B, F]")
@@ -139,14 +153,26 @@ class Context:
         # (a report makes the call wait for the device: only when asked, so that an AFS_ASYNC context's
         # calls with device buffers return once queued)
         rep = _native.AfsReport()
-        st = self._lib.afs_synthesize(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop,
-                                      _vp(_addr(out)), _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
-        _native.check(st, self._h, "afs_synthesize")
+        if taps:
+            nt = getattr(self, "n_taps", 0)
+            if taps_out is None:
+                taps_out = np.zeros((B, nt, T), dtype=np.float64)
+            if nt and _nbytes(taps_out) != B * nt * T * 8:  # (no taps set: the library refuses the call)
+                raise ValueError("taps_out must hold B*n_taps*(F-1)*hop doubles")
+            st = self._lib.afs_synthesize_taps(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop,
+                                               _vp(_addr(out)), _vp(_addr(taps_out)), _vp(_addr(nonfinite)),
+                                               ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize_taps")
+        else:
+            st = self._lib.afs_synthesize(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop,
+                                          _vp(_addr(out)), _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize")
+        res = (out, taps_out) if taps else (out,)
         if report:
-            return out, {"device_ms": rep.device_ms, "samples": rep.samples,
-                         "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
-                         "nonfinite": nonfinite}
-        return out
+            res += ({"device_ms": rep.device_ms, "samples": rep.samples,
+                     "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                     "nonfinite": nonfinite},)
+        return res if len(res) > 1 else res[0]
 
     def noise_plans(self, frames: np.ndarray, hop: int, s_begin: int = 0, s_end: Optional[int] = None) -> np.ndarray:
         """Diagnostics (tree solver): the noise-source plan records K5 computes for samples
@@ -298,6 +324,55 @@ class Context:
         return out
 
 
+# Names of the usual taps: (kind, index) in the reference's numbering.  Branch current c flows into
+# section c for c < Tube::NUM_SECTIONS = 93 (TdsModel.cpp:93-98); the sections are Tube.h:53-79's.
+TAPS = {
+    # the flow through the glottis: the current into the upper glottis section 24 out of the lower
+    # one, 23 (TdsModel.cpp:96-97, sourceSection = i - 1; Tube.h:66-67 the glottis sections)
+    "glottal_flow": (_native.AFS_TAP_CURRENT, 24),
+    # the two currents from the mouth opening into free space (TdsModel.cpp:115-121: NUM_SECTIONS,
+    # NUM_SECTIONS + 1, source LAST_MOUTH_SECTION): through the radiation resistance and inductance
+    "mouth_radiation_r": (_native.AFS_TAP_CURRENT, 93),
+    "mouth_radiation_l": (_native.AFS_TAP_CURRENT, 94),
+    # the two currents from the nostrils into free space (TdsModel.cpp:125-131: NUM_SECTIONS + 2, + 3)
+    "nostril_radiation_r": (_native.AFS_TAP_CURRENT, 95),
+    "nostril_radiation_l": (_native.AFS_TAP_CURRENT, 96),
+    # the flow into the nose: FIRST_NOSE_SECTION's current, out of LAST_PHARYNX_SECTION (TdsModel.cpp:103)
+    "nasal_flow": (_native.AFS_TAP_CURRENT, 65),
+    # the subglottal pressure: LAST_TRACHEA_SECTION (Tube.h:74; section 22)
+    "subglottal_pressure": (_native.AFS_TAP_PRESSURE, 22),
+}
+FIRST_PHARYNX_SECTION, FIRST_MOUTH_SECTION = 25, 41  # Tube.h:68-69
+NUM_PHARYNX_MOUTH_SECTIONS = 40
+
+
+def pharynx_mouth_pressure(i: int):
+    """The pressure tap of pharynx/mouth section ``i`` (0 .. 39: the index of afs_frame's area_cm2;
+    Tube section FIRST_PHARYNX_SECTION + i, Tube.h:68-69), e.g. the intra-oral
+    pressure behind a constriction at section i + 1."""
+    if not 0 <= int(i) < NUM_PHARYNX_MOUTH_SECTIONS:
+        raise ValueError("pharynx/mouth sections are 0 .. 39")
+    return (_native.AFS_TAP_PRESSURE, FIRST_PHARYNX_SECTION + int(i))
+
+
+def tap(t):
+    """(kind, index) of a tap given as a name of TAPS, ("pressure" | "current", index) or (kind, index)."""
+    if isinstance(t, str):
+        return TAPS[t]
+    kind, index = t
+    if isinstance(kind, str):
+        kind = {"pressure": _native.AFS_TAP_PRESSURE, "current": _native.AFS_TAP_CURRENT}[kind]
+    return int(kind), int(index)
+
+
+def section_currents(section: int):
+    """TdsModel's getCurrentIn / getCurrentOut topology: (in, (out0, out1)) of a section, -1: none."""
+    cin, cout = ctypes.c_int32(), (ctypes.c_int32 * 2)()
+    _native.check(_native.load().afs_section_currents(int(section), ctypes.byref(cin), cout), None,
+                  "afs_section_currents")
+    return cin.value, (cout[0], cout[1])
+
+
 def shard_range(total: int, world: int, rank: int):
     """afs_shard_range: (first, count) of ``rank``'s contiguous block of ``total`` utterances."""
     f, n = ctypes.c_int64(), ctypes.c_int64()
@@ -445,11 +520,19 @@ class Synthesizer:
         s = np.arange(1, self.batch + 1, dtype=np.uint32) if seeds is None else np.asarray(seeds, dtype=np.uint32)
         _native.check(self._lib.afs_session_reset(self._h, _vp(_addr(s))), self.ctx.handle, "afs_session_reset")
 
-    def synthesize_signal_tds(self, frames: np.ndarray, num_samples: int) -> np.ndarray:
+    def synthesize_signal_tds(self, frames: np.ndarray, num_samples: int, taps: bool = False):
+        """``taps=True``: returns (audio, taps[batch, n_taps, produced]) with the context's taps
+        (:meth:`Context.set_taps`) after every sample."""
         fr = np.ascontiguousarray(np.broadcast_to(frames, (self.batch,)), dtype=FRAME_DTYPE)
         n = max(int(num_samples), 1)
         out = np.zeros((self.batch, n), dtype=np.float64)
         produced = ctypes.c_int32(0)
+        if taps:
+            tout = np.zeros((self.batch, getattr(self.ctx, "n_taps", 0), n), dtype=np.float64)
+            st = self._lib.afs_session_synthesize_taps(self._h, _vp(_addr(fr)), int(num_samples), _vp(_addr(out)),
+                                                       _vp(_addr(tout)), None, ctypes.byref(produced), None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_taps")
+            return out[:, : produced.value], tout[:, :, : produced.value]
         st = self._lib.afs_session_synthesize(self._h, _vp(_addr(fr)), int(num_samples), _vp(_addr(out)), None,
                                               ctypes.byref(produced), None)
         _native.check(st, self.ctx.handle, "afs_session_synthesize")

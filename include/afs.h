@@ -272,6 +272,41 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds);
 afs_status afs_session_rng_draws(afs_session *s, int64_t *draws);
 void afs_session_destroy(afs_session *s);
 
+/* ---- Signal taps: section pressures and branch currents beside the audio -----------------
+ * TdsModel::getSectionPressure / getSectionFlow (TdsModel.cpp:1715-1734) for whole batches: up to
+ * AFS_MAX_TAPS quantities of the tube's state, one value per audio sample.  Value t of a tap is the
+ * state after sample t's proceedTimeStep, which is what the reference's getters return at that moment.
+ * Sections and currents keep the reference's numbering (Tube.h:53-82; TdsModel.cpp:93-131: current c
+ * flows into section c for c < 93, 93/94 leave the mouth, 95/96 the nostrils).
+ * Tree solver only (the one-lane solvers: AFS_ERR_UNSUPPORTED).  afs_set_taps validates the list
+ * (AFS_ERR_INVALID_ARGUMENT: n outside 0..AFS_MAX_TAPS, an unknown kind, an index outside its range)
+ * and keeps it in the context until it is set again; n = 0 clears it.  The _taps calls are
+ * afs_synthesize / afs_session_synthesize with one more output, taps_out[batch][n_taps][T] doubles
+ * (host or device; T the call's samples per utterance, as for out); without a list they answer
+ * AFS_ERR_INVALID_ARGUMENT.  Their audio is the plain calls' bit for bit, AFS_ASYNC treats taps_out as
+ * it treats out (a device taps_out does not wait), and an utterance that goes non-finite carries the
+ * NaN in its tap rows as in its audio.  afs_synthesize and afs_session_synthesize ignore the list.
+ * afs_play_target_sequences and afs_multi_synthesize have no _taps form. */
+#define AFS_MAX_TAPS 8
+typedef enum afs_tap_kind {
+  AFS_TAP_PRESSURE = 0, /* tubeSection[index].pressure (dPa),         index 0..92 */
+  AFS_TAP_CURRENT = 1   /* branchCurrent[index].magnitude (cm^3/s),   index 0..96 */
+} afs_tap_kind;
+typedef struct afs_tap {
+  int32_t kind;  /* afs_tap_kind */
+  int32_t index;
+} afs_tap;
+afs_status afs_set_taps(afs_ctx *ctx, const afs_tap *taps, int32_t n);
+afs_status afs_synthesize_taps(afs_ctx *ctx, const afs_frame *frames, const uint32_t *seeds, int32_t batch,
+                               int32_t num_frames, int32_t hop, double *out, double *taps_out,
+                               uint8_t *nonfinite, afs_report *report);
+afs_status afs_session_synthesize_taps(afs_session *s, const afs_frame *frames, int32_t num_samples, double *out,
+                                       double *taps_out, uint8_t *nonfinite, int32_t *produced,
+                                       afs_report *report);
+/* getCurrentIn / getCurrentOut's topology (TdsModel.cpp:139-203): the branch currents that flow into
+ * and out of a section, -1 where there is none.  Needs no context. */
+afs_status afs_section_currents(int32_t section, int32_t *in, int32_t out[2]);
+
 /* Area-function model -> tube frames (pharynx/mouth part, teeth).  params[n][16] in
  * OneDimAreaFunction::ParamIndex order; velum and glottis fields of frames are left unchanged. */
 afs_status afs_af_to_frames(afs_ctx *ctx, const double *params, int64_t n, afs_frame *frames);
