@@ -42,6 +42,7 @@ EXPORTED = (
     "afs_shard_range", "afs_comm_unique_id", "afs_comm_create", "afs_comm_create_all", "afs_comm_destroy",
     "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times", "afs_multi_synthesize",
     "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps", "afs_section_currents",
+    "afs_synthesize_ragged",
 )
 
 
@@ -158,13 +159,15 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_session_synthesize_taps.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(AfsReport)]
     lib.afs_section_currents.argtypes = [ctypes.c_int32, i32p, i32p]
+    lib.afs_synthesize_ragged.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32, vp,
+                                          ctypes.c_int64, vp, vp, ctypes.POINTER(AfsReport)]
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",
                  "afs_to_int16", "afs_play_target_sequences", "afs_rng_draws", "afs_session_rng_draws", "afs_plan_hop_words",
                  "afs_kernel_times", "afs_kernel_times_ex", "afs_comm_unique_id", "afs_comm_create", "afs_comm_create_all",
                  "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times",
                  "afs_multi_synthesize", "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps",
-                 "afs_section_currents"):
+                 "afs_section_currents", "afs_synthesize_ragged"):
         getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -21,6 +21,7 @@
 #include "afs_audio.h"
 #include "afs_ctx.h"
 #include "afs_model.h"
+#include "afs_ragged_order.h"
 #include "afs_tree.h"
 #include "afs_xcd_order.h"
 
@@ -157,6 +158,12 @@ struct SynthCall {
   // the _taps calls: tap k of utterance u to taps[(u * n_taps + k) * tstride + s] (null: no taps)
   double *taps = nullptr;
   int64_t tstride = 0;
+  // afs_synthesize_ragged (device arrays; null: every utterance plays all ntrans transitions):
+  // utterance u plays row_hops[u] of them, ntrans the longest's; block_end and pad_standin belong to
+  // the slot order so.order (afs_ragged_order.h)
+  const int32_t *row_hops = nullptr;
+  const int64_t *block_end = nullptr;
+  const int32_t *pad_standin = nullptr;
 };
 
 // the context's tap list as K1 reads it: a current from the slot the solver leaves it in, a
@@ -225,13 +232,16 @@ afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, in
     a.tap_out = call.taps + s0;
     a.tap_stride = call.tstride;
   }
+  a.block_end = call.block_end;
+  a.pad_standin = call.pad_standin;
   hipEvent_t e1 = prof_event(c);
   HIP_TRY(c, afs::launch_tree_synth(a, call.width, c->stream));
   hipEvent_t e2 = prof_event(c);
   prof_pair(c, e1, e2, 0);
   // K6: the glottal-tone filter and the output stage of the launch's samples
   HIP_TRY(c, afs::launch_tree_output(c->dev_tab, (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
-                                     c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap));
+                                     c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap,
+                                     call.row_hops, call.hop, s0));
   prof_pair(c, e2, prof_event(c), 2);
   return AFS_OK;
 }
@@ -273,6 +283,7 @@ afs_status run_hop_call(afs_ctx *c, const SynthCall &call, bool *done) {
   pa.hop_stride = hstride;
   pa.work = work;
   pa.compact = true;
+  pa.row_hops = call.row_hops;
   hipEvent_t e0 = prof_event(c);
   HIP_TRY(c, afs::launch_plan_hops_iv(pa, c->stream));
   // Slots for the mixed hops: one for every hop of the call when they fit the budget (small calls:
@@ -350,6 +361,7 @@ afs_status run_chunked(afs_ctx *c, const SynthCall &call) {
     pa.work = hops ? (uint32_t *)c->plan_work : nullptr;
     pa.compact = hops;
     pa.dense_cap = (int64_t)rows * hstride;  // (hop mode: a slot for every hop of the chunk)
+    pa.row_hops = call.row_hops;
     hipEvent_t e0 = prof_event(c);
     HIP_TRY(c, hops ? afs::launch_plan_hops(pa, c->stream) : afs::launch_plan(pa, c->stream));
     prof_pair(c, e0, prof_event(c), 1);
@@ -493,17 +505,18 @@ afs_status fill_report(afs_ctx *c, afs_report *rep, int64_t samples) {
 // The end of a whole-trajectory call on the context's state: ev1, the non-finite flags and count, the
 // copy of staged audio to a host `out`, then the wait and the report.  The call returns without a
 // wait only when it is asynchronous (`async`) and nothing goes to host memory: no host `out`, no
-// report, no host flags.
-afs_status finish_call(afs_ctx *c, int B, int64_t T, double *out, const double *dout, bool host_out,
-                       uint8_t *nonfinite, afs_report *rep, bool async) {
+// report, no host flags.  `elems`: the doubles of out (rows and their stride); `samples`: what the
+// report counts.
+afs_status finish_call(afs_ctx *c, int B, int64_t elems, int64_t samples, double *out, const double *dout,
+                       bool host_out, uint8_t *nonfinite, afs_report *rep, bool async) {
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   c->last_B = B;
   bool nf_sync = false;
   afs_status s = nonfinite_report(c, c->ws, pad64(B), B, nonfinite, rep != nullptr, &nf_sync);
   if (s != AFS_OK) return s;
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (!async || host_out || rep || nf_sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return fill_report(c, rep, (int64_t)B * T);
+  return fill_report(c, rep, samples);
 }
 
 afs_status draws_of(afs_ctx *c, const void *ws, int B, int64_t *draws) {
@@ -614,7 +627,8 @@ void afs_destroy(afs_ctx *c) {
   if (c->dev_tab) (void)hipFree(c->dev_tab);
   if (c->dcount) (void)hipFree(c->dcount);
   if (c->hcount) (void)hipHostFree(c->hcount);
-  for (hipEvent_t e : {c->ev_k5, c->ev0, c->ev1})
+  if (c->ragged_host) (void)hipHostFree(c->ragged_host);
+  for (hipEvent_t e : {c->ev_k5, c->ev_ragged, c->ev0, c->ev1})
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
   delete c;
@@ -727,7 +741,100 @@ static afs_status synth_core(afs_ctx *c, const afs_frame *frames, const uint32_t
   // (a host taps_out is copied back as a host out is, and the call then waits)
   if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
   const bool async = (force_async || (c->cfg.flags & AFS_ASYNC)) && !host_taps;
-  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, async);
+  return finish_call(c, B, (int64_t)B * T, (int64_t)B * T, out, dout, host_out, nonfinite, rep, async);
+}
+
+// The launch layout of a ragged call and its per-row hop counts on the device: built on the host from
+// num_frames (afs_ragged_order.h), packed into the context's pinned buffer and uploaded on the stream
+// -- no host wait, except for the previous ragged call's upload when that has not been read yet.
+static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, int upb, int hop, SynthCall *call) {
+  const afs::RaggedOrder ro = afs::ragged_order(num_frames, B, upb, hop);
+  const size_t slots = ro.order.size();
+  const size_t end_bytes = (size_t)ro.grid * sizeof(int64_t), slot_bytes = slots * sizeof(int32_t);
+  const size_t bytes = end_bytes + 2 * slot_bytes + (size_t)B * sizeof(int32_t);
+  if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
+  if (bytes > c->ragged_host_bytes) {
+    if (c->ragged_host) (void)hipHostFree(c->ragged_host);
+    c->ragged_host = nullptr;
+    c->ragged_host_bytes = 0;
+    HIP_TRY(c, hipHostMalloc(&c->ragged_host, bytes, hipHostMallocDefault));
+    c->ragged_host_bytes = bytes;
+  }
+  const afs_status s = ensure(c, &c->ragged, &c->ragged_bytes, bytes);
+  if (s != AFS_OK) return s;
+  char *h = (char *)c->ragged_host, *d = (char *)c->ragged;
+  std::memcpy(h, ro.block_end.data(), end_bytes);
+  std::memcpy(h + end_bytes, ro.order.data(), slot_bytes);
+  std::memcpy(h + end_bytes + slot_bytes, ro.standin.data(), slot_bytes);
+  int32_t *hops = (int32_t *)(h + end_bytes + 2 * slot_bytes);
+  for (int u = 0; u < B; ++u) hops[u] = num_frames[u] - 1;
+  HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  call->block_end = (const int64_t *)d;
+  call->so.order = (const int32_t *)(d + end_bytes);
+  call->so.grid = ro.grid;
+  call->pad_standin = (const int32_t *)(d + end_bytes + slot_bytes);
+  call->row_hops = (const int32_t *)(d + end_bytes + 2 * slot_bytes);
+  return AFS_OK;
+}
+
+// afs_synthesize_ragged: synth_core for utterances of different lengths.  One call of ntrans = the
+// longest utterance's transitions; K1's blocks each hold one length and end their time loop there
+// (ragged_layout), K5 and K6 stop at each row's own end.  The slot order by shape inside a length
+// group is left out.
+static afs_status synth_ragged(afs_ctx *c, const afs_frame *frames, int64_t fstride, const int32_t *num_frames,
+                               const uint32_t *seeds, int32_t B, int32_t hop, double *out, int64_t ostride,
+                               double *taps_out, uint8_t *nonfinite, afs_report *rep) {
+  const char *fn = "afs_synthesize_ragged";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!frames || !out || B <= 0 || hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, out, batch>0, hop>=1", fn);
+  if (!num_frames || is_device_ptr(num_frames))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
+  int32_t Fmax = 0;
+  int64_t total = 0;
+  for (int32_t u = 0; u < B; ++u) {
+    const int32_t F = num_frames[u];
+    if (F < 2 || F > fstride)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 2..frame_stride = %lld", fn, u, F,
+                  (long long)fstride);
+    Fmax = std::max(Fmax, F);
+    total += (int64_t)(F - 1) * hop;
+  }
+  const int64_t Tmax = (int64_t)(Fmax - 1) * hop;
+  if (ostride < Tmax)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out_stride %lld below the longest utterance's %lld samples", fn,
+                (long long)ostride, (long long)Tmax);
+  if (taps_out && c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  afs_status s;
+  const afs_frame *dframes;
+  const uint32_t *dseeds;
+  double *dout, *dtaps = nullptr;
+  bool host_out, host_taps = false;
+  const size_t out_bytes = (size_t)B * (size_t)ostride * sizeof(double), taps_bytes = out_bytes * (size_t)c->n_taps;
+  if ((s = frames_to_device(c, frames, (size_t)B * (size_t)fstride, &dframes)) != AFS_OK) return s;
+  if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
+  if ((s = device_out(c, out, (size_t)B * (size_t)ostride, &dout, &host_out)) != AFS_OK) return s;
+  // (a host out goes up first and comes back whole: what lies past each row's end is the caller's)
+  if (host_out) HIP_TRY(c, hipMemcpyAsync(dout, out, out_bytes, hipMemcpyHostToDevice, c->stream));
+  const int width = lanes_for(c, B);
+  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  if (taps_out) {
+    if ((s = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps, &host_taps)) != AFS_OK)
+      return s;
+    if (host_taps) HIP_TRY(c, hipMemcpyAsync(dtaps, taps_out, taps_bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  SynthCall call{dframes, fstride, B, Fmax - 1, hop, dout, ostride, c->ws, c->rng, c->tree_lanes, pad64(B), B, width,
+                 nullptr, plain_order(c)};
+  call.taps = dtaps;
+  call.tstride = ostride;
+  if ((s = ragged_layout(c, num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, hop, &call)) != AFS_OK) return s;
+  if ((s = run_call(c, call)) != AFS_OK) return s;
+  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
+  const bool async = (c->cfg.flags & AFS_ASYNC) && !host_taps;
+  return finish_call(c, B, (int64_t)B * ostride, total, out, dout, host_out, nonfinite, rep, async);
 }
 
 afs_status afs::synthesize_async(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
@@ -768,6 +875,13 @@ afs_status afs_synthesize_taps(afs_ctx *c, const afs_frame *frames, const uint32
   const afs_status s = taps_check(c, "afs_synthesize_taps", taps_out);
   if (s != AFS_OK) return s;
   return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, rep, false, 0, taps_out);
+}
+
+afs_status afs_synthesize_ragged(afs_ctx *c, const afs_frame *frames, int64_t frame_stride, const int32_t *num_frames,
+                                 const uint32_t *seeds, int32_t B, int32_t hop, double *out, int64_t out_stride,
+                                 double *taps_out, uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  return synth_ragged(c, frames, frame_stride, num_frames, seeds, B, hop, out, out_stride, taps_out, nonfinite, rep);
 }
 
 afs_status afs_section_currents(int32_t section, int32_t *in, int32_t out[2]) {
@@ -1272,7 +1386,8 @@ afs_status afs_play_target_sequences(afs_ctx *c, const double *shapes, int32_t n
     call.so.order = dord;
     if ((s = run_call(c, call)) != AFS_OK) return s;
   }
-  return finish_call(c, B, T, out, dout, host_out, nonfinite, rep, (c->cfg.flags & AFS_ASYNC) != 0);
+  return finish_call(c, B, (int64_t)B * T, (int64_t)B * T, out, dout, host_out, nonfinite, rep,
+                     (c->cfg.flags & AFS_ASYNC) != 0);
 }
 
 }  // extern "C"

@@ -69,6 +69,14 @@ struct afs_ctx {
   int32_t n_taps = 0;
   void *stage_taps = nullptr;
   size_t stage_taps_bytes = 0;
+  // afs_synthesize_ragged: the call's launch layout (afs_ragged_order.h) and per-row hop counts on
+  // the device, the pinned host copy they are uploaded from on the stream, and the event after that
+  // upload (the next ragged call rewrites the host copy only once it has been read)
+  void *ragged = nullptr;
+  size_t ragged_bytes = 0;
+  void *ragged_host = nullptr;
+  size_t ragged_host_bytes = 0;
+  hipEvent_t ev_ragged = nullptr;
   int32_t last_B = 0;        // batch of the last whole-trajectory call (afs_rng_draws)
   int32_t *dcount = nullptr;
   int32_t *hcount = nullptr;  // pinned host copy of dcount

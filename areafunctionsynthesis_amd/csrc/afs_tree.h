@@ -63,6 +63,12 @@ struct TreeArgs {
   TapSet taps{};
   double *tap_out = nullptr;
   int64_t tap_stride = 0;
+  // utterances of different lengths (afs_capi.cpp synth_ragged, afs_ragged_order.h; null: every block
+  // runs to s_end): block b's time loop ends at sample min(s_end, block_end[b]) of the call -- its
+  // utterances all end there -- and a block that ended before s_begin exits at once; a padding slot
+  // reads the data of utterance pad_standin[slot], a live one of its own block, instead of utterance 0's
+  const int64_t *block_end = nullptr;
+  const int32_t *pad_standin = nullptr;
 };
 // K5: the noise-source plans of samples [s_begin, s_end) of `rows` frame rows.
 struct PlanArgs {
@@ -87,6 +93,10 @@ struct PlanArgs {
   // instead of sample-indexed rows (the diagnostics' layout)
   bool compact = false;
   int64_t dense_cap = 0;
+  // utterances of different lengths: row r plays hops 0 .. row_hops[r] - 1 only (null: every hop of
+  // the launch).  A (row, hop) or (row, sample) past the row's end is skipped before any of its frames
+  // is read: it gets no record, is never listed and claims no dense slot.
+  const int32_t *row_hops = nullptr;
 };
 constexpr int64_t PLAN_RECORD_BYTES = 128;
 // Hop slots a launch of samples [s0, s1) spans.
@@ -141,9 +151,12 @@ hipError_t launch_tree_synth(const TreeArgs &a, int lanes, hipStream_t st);
 // section-25 pressures (p25, skin != 0) and the output stage over the flows the launch stored
 // (out[u * out_stride + s - s_begin], replaced by the audio).
 // (skip_claims: as TreeArgs::skip_claims -- the launch does nothing when *skip_claims > skip_cap)
+// (row_hops: utterances of different lengths -- utterance u ends at sample row_hops[u] * hop of the
+// call and filters min(n, that - s_begin) samples of this launch, none when that is <= 0)
 hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out, int64_t out_stride, int64_t n, int B,
                               const double *p25, int64_t p25_stride, int skin, hipStream_t st,
-                              const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0);
+                              const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0,
+                              const int32_t *row_hops = nullptr, int hop = 0, int64_t s_begin = 0);
 // Load the tree kernels' and K5's code objects on the current device (afs_create: no code-object
 // load inside the first synthesis call).
 hipError_t preload_tree_kernels();

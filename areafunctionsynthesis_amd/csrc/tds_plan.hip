@@ -29,9 +29,14 @@ static_assert(sizeof(afs_frame) % 8 == 0, "frames are copied as 8-byte words");
 
 __global__ void __launch_bounds__(PLAN_BLOCK) plan_kernel(PlanArgs a) {
   __shared__ uint64_t fr_lds[PLAN_STAGE][FRAME_WORDS];
-  const int64_t n = a.s_end - a.s_begin;
+  int64_t n = a.s_end - a.s_begin;
   const int64_t row = blockIdx.x;
   const int64_t t_first = (int64_t)blockIdx.y * PLAN_BLOCK;
+  if (a.row_hops) {  // (the row ends inside the launch or before it: the block's samples up to there)
+    const int64_t left = (int64_t)a.row_hops[row] * a.hop - a.s_begin;
+    n = left < n ? left : n;
+    if (n <= t_first) return;  // (uniform over the block; before any frame is read)
+  }
   const int64_t t_last = (t_first + PLAN_BLOCK < n ? t_first + PLAN_BLOCK : n) - 1;
   const int64_t t = t_first + threadIdx.x;
   const afs_frame *f = a.frames + row * a.frame_stride;
@@ -118,7 +123,15 @@ __global__ void __launch_bounds__(HOP_IV_BLOCK) plan_hop_iv_kernel(PlanArgs a, i
   if (staged) {
     const uint64_t *src = (const uint64_t *)(a.frames + f0);
     const int words = (int)(f1 - f0 + 1) * FRAME_WORDS;
-    for (int w = threadIdx.x; w < words; w += HOP_IV_BLOCK) (&fr_lds[0][0])[w] = src[w];
+    if (a.row_hops) {  // (frame by frame: a frame past its row's end is not read, its LDS copy never used)
+      for (int j = 0; j < (int)(f1 - f0 + 1); ++j) {
+        const int64_t f = f0 + j;
+        if (f % a.frame_stride > a.row_hops[f / a.frame_stride]) continue;
+        for (int w = threadIdx.x; w < FRAME_WORDS; w += HOP_IV_BLOCK) fr_lds[j][w] = src[j * FRAME_WORDS + w];
+      }
+    } else {
+      for (int w = threadIdx.x; w < words; w += HOP_IV_BLOCK) (&fr_lds[0][0])[w] = src[w];
+    }
     __syncthreads();
     for (int q = threadIdx.x; q < (int)(f1 - f0 + 1) * NPM; q += HOP_IV_BLOCK) {
       double *ar = ((afs_frame *)fr_lds[q / NPM])->area_cm2 + q % NPM;
@@ -129,6 +142,7 @@ __global__ void __launch_bounds__(HOP_IV_BLOCK) plan_hop_iv_kernel(PlanArgs a, i
   if (id >= n_ids) return;
   const int64_t row = id / slots, slot = id % slots;
   const HopRange r = hop_range(a, slot);
+  if (a.row_hops && r.h >= a.row_hops[row]) return;  // (past the row's end: no record, not listed)
   PlanKey k;
   bool ok;
   const afs_frame *fl, *fr;

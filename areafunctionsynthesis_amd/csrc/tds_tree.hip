@@ -19,6 +19,14 @@ __global__ void __launch_bounds__(64 * Geom<W>::WPB, AFS_TREE_MIN_WAVES) tree_sy
   tree_synth_body<false, MODEL, HOPS, W, TAPS>(a, lds, nullptr);
 }
 
+// ... and the forms a ragged call launches (TreeArgs::block_end, pad_standin; afs_synthesize_ragged):
+// kernels of their own, as TAPS has, so that the uniform calls' kernels stay what they were
+template <int MODEL, bool HOPS, int W, bool TAPS = false>
+__global__ void __launch_bounds__(64 * Geom<W>::WPB, AFS_TREE_MIN_WAVES) tree_synth_ragged_kernel(TreeArgs a) {
+  __shared__ WaveLdsT<W> lds;
+  tree_synth_body<false, MODEL, HOPS, W, TAPS, true>(a, lds, nullptr);
+}
+
 #if AFS_PAIR
 // the wave-pair build of the throughput kernel (tree_kernel.h tree_pair_body): four waves per
 // workgroup, two per SIMD
@@ -33,6 +41,17 @@ template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(128, 2) tree_pair64_kernel(TreeArgs a) {
   __shared__ WaveLdsT<64> lds;
   tree_pair64_body<MODEL, HOPS, false, TAPS>(a, lds);
+}
+template <int MODEL, bool HOPS, bool TAPS = false>
+__global__ void __launch_bounds__(256, 2) tree_pair_ragged_kernel(TreeArgs a) {
+  __shared__ WaveLdsT<TW> lds;
+  __shared__ int pattern[5];
+  tree_pair_body<MODEL, HOPS, false, TAPS, true>(a, lds, pattern);
+}
+template <int MODEL, bool HOPS, bool TAPS = false>
+__global__ void __launch_bounds__(128, 2) tree_pair64_ragged_kernel(TreeArgs a) {
+  __shared__ WaveLdsT<64> lds;
+  tree_pair64_body<MODEL, HOPS, false, TAPS, true>(a, lds);
 }
 #endif
 
@@ -53,6 +72,25 @@ __global__ void __launch_bounds__(64) tree_output_kernel(const Tables *tab, doub
   double *o = out + (int64_t)u * out_stride;
   if (p25 && skin) tone_output_run(X, tab->consts, p25 + (int64_t)u * p25_stride, o, (int)n);
   else output_filter_run(X, tab->consts, o, (int)n);
+}
+// K6 of a ragged call: utterance u ends at sample row_hops[u] * hop of the call, so of this launch's n
+// samples from s_begin it filters those K1 stored for it (TreeArgs::block_end) -- none once it has ended
+__global__ void __launch_bounds__(64) tree_output_ragged_kernel(const Tables *tab, double *lds_state, double *out,
+                                                                int64_t out_stride, int64_t n, int B, const double *p25,
+                                                                int64_t p25_stride, int skin,
+                                                                const uint32_t *skip_claims, int64_t skip_cap,
+                                                                const int32_t *row_hops, int hop, int64_t s_begin) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  const int64_t left = (int64_t)row_hops[u] * hop - s_begin;
+  n = left < n ? left : n;
+  if (n <= 0) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  double *o = out + (int64_t)u * out_stride;
+  // (tone_output_run / output_filter_run in instantiations of this kernel's own: tree_core.h FORM)
+  if (p25 && skin) output_filter_run_t<true, 1>(X, tab->consts, o, (int)n, p25 + (int64_t)u * p25_stride);
+  else output_filter_run_t<false, 1>(X, tab->consts, o, (int)n, nullptr);
 }
 
 // seeds == nullptr: utterance u is seeded u + 1 (afs.h)
@@ -135,10 +173,15 @@ hipError_t launch_tree_interp(const Tables *tab, const afs_frame *fl, const afs_
 
 hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out, int64_t out_stride, int64_t n, int B,
                               const double *p25, int64_t p25_stride, int skin, hipStream_t st,
-                              const uint32_t *skip_claims, int64_t skip_cap) {
+                              const uint32_t *skip_claims, int64_t skip_cap, const int32_t *row_hops, int hop,
+                              int64_t s_begin) {
   if (B <= 0 || n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(tree_output_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, out, out_stride, n, B,
-                     p25, p25_stride, skin, skip_claims, skip_cap);
+  if (row_hops)
+    hipLaunchKernelGGL(tree_output_ragged_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, out, out_stride,
+                       n, B, p25, p25_stride, skin, skip_claims, skip_cap, row_hops, hop, s_begin);
+  else
+    hipLaunchKernelGGL(tree_output_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, out, out_stride, n, B,
+                       p25, p25_stride, skin, skip_claims, skip_cap);
   return hipGetLastError();
 }
 
@@ -171,40 +214,52 @@ static void launch_model_hops(const TreeArgs &a, dim3 grid, dim3 block, hipStrea
 }
 
 // the one-wave kernel (every phase on one wave)
-template <int W, bool TAPS>
+template <int W, bool TAPS, bool RAGGED>
 static void launch_one_wave(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st) {
-  launch_model_hops(a, grid, block, st, [](auto m, auto h) { return tree_synth_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>; });
+  launch_model_hops(a, grid, block, st, [](auto m, auto h) {
+    if constexpr (RAGGED) return tree_synth_ragged_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>;
+    else return tree_synth_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>;
+  });
 }
 
-template <int W, bool TAPS>
+template <int W, bool TAPS, bool RAGGED>
 static void launch_synth_w(const TreeArgs &a, hipStream_t st) {
   constexpr int UPB_ = Geom<W>::UPB;
   const dim3 grid(a.grid_blocks > 0 ? a.grid_blocks : (a.B + UPB_ - 1) / UPB_), block(64 * Geom<W>::WPB);
 #if AFS_PAIR
   if constexpr (W == TW) {  // (the one-wave kernel at 16 lanes is not instantiated in this build)
     static_assert(Geom<TW>::WPB == 2, "a wave pair per four utterances: 4 waves per 8-utterance block");
-    launch_model_hops(a, grid, dim3(256), st, [](auto m, auto h) { return tree_pair_kernel<decltype(m)::value, decltype(h)::value, TAPS>; });
+    launch_model_hops(a, grid, dim3(256), st, [](auto m, auto h) {
+      if constexpr (RAGGED) return tree_pair_ragged_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
+      else return tree_pair_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
+    });
   } else if constexpr (W == 64) {
     if (a.B <= TREE_PAIR64_MAX) {
-      launch_model_hops(a, grid, dim3(128), st, [](auto m, auto h) { return tree_pair64_kernel<decltype(m)::value, decltype(h)::value, TAPS>; });
+      launch_model_hops(a, grid, dim3(128), st, [](auto m, auto h) {
+        if constexpr (RAGGED) return tree_pair64_ragged_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
+        else return tree_pair64_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
+      });
       return;
     }
   }
-  if constexpr (W != TW) launch_one_wave<W, TAPS>(a, grid, block, st);
+  if constexpr (W != TW) launch_one_wave<W, TAPS, RAGGED>(a, grid, block, st);
 #else
-  launch_one_wave<W, TAPS>(a, grid, block, st);
+  launch_one_wave<W, TAPS, RAGGED>(a, grid, block, st);
 #endif
 }
 
 hipError_t launch_tree_synth(const TreeArgs &a, int lanes, hipStream_t st) {
   if (a.B <= 0 || a.s_end <= a.s_begin) return hipSuccess;
+  // (a ragged launch carries both arrays and a slot order with a block count: afs_ragged_order.h)
+  const bool ragged = a.block_end || a.pad_standin;
+  if (ragged && !(a.block_end && a.pad_standin && a.order && a.grid_blocks > 0)) return hipErrorInvalidValue;
   if (a.taps.n > 0) {
     if (a.taps.n > AFS_MAX_TAPS || !a.tap_out) return hipErrorInvalidValue;
-    if (lanes == 64) launch_synth_w<64, true>(a, st);
-    else launch_synth_w<TW, true>(a, st);
+    if (lanes == 64) ragged ? launch_synth_w<64, true, true>(a, st) : launch_synth_w<64, true, false>(a, st);
+    else ragged ? launch_synth_w<TW, true, true>(a, st) : launch_synth_w<TW, true, false>(a, st);
   } else {
-    if (lanes == 64) launch_synth_w<64, false>(a, st);
-    else launch_synth_w<TW, false>(a, st);
+    if (lanes == 64) ragged ? launch_synth_w<64, false, true>(a, st) : launch_synth_w<64, false, false>(a, st);
+    else ragged ? launch_synth_w<TW, false, true>(a, st) : launch_synth_w<TW, false, false>(a, st);
   }
   return hipGetLastError();
 }

@@ -2170,7 +2170,9 @@ AFS_HD inline double output_filter_one(double *X, const Consts &C, double flow) 
 // 25's new pressure of sample i, its output added to the flow o[i] (the same operations as
 // phase_output, so bitwise the same audio): one loop, so that the tone chain of sample i + 1 and
 // the output filter's chain of sample i (independent) overlap, instead of two runs back to back.
-template <bool TONE>
+// FORM: a tag only -- a second kernel of a file takes an instantiation of its own (tds_tree.hip, K6 of
+// the ragged calls), so that each kernel stays the one caller of its copy and is compiled as before.
+template <bool TONE, int FORM = 0>
 AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, int n, const double *p25) {
   // (not contracted into fmas: each product and sum rounds as in the reference, so the result does
   // not depend on where a run starts -- a session's per-call runs equal one run over the whole

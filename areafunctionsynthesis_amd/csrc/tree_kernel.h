@@ -219,9 +219,34 @@ using WaveLds = WaveLdsT<TW>;
 // Whether this block has anything to do: not a launch of the hop-mode fast path whose mixed hops
 // overflowed K5's compact slots (the host runs the call through the chunked path instead,
 // afs_capi.cpp run_chunks), and not a block of padding slots only (the XCD-dealt slot order).
-template <int W>
+// Utterances of different lengths (TreeArgs::block_end): the sample of the call at which this block's
+// time loop ends in this launch -- its utterances' own end when that comes first -- and the utterance
+// whose data a slot reads (a padding slot: a live utterance of its own block, else utterance 0).
+// Block-uniform, set once before the time loop.  RAGGED: the kernels' forms that a ragged call
+// launches (tds_tree.hip) -- the uniform kernels read neither array and hold none of this code: with a
+// run-time null check instead, their register counts and scratch sizes moved.
+template <bool RAGGED>
+__device__ __forceinline__ int64_t block_s_end(const TreeArgs &a) {
+  if constexpr (RAGGED) {
+    const int64_t e = a.block_end[blockIdx.x];
+    return e < a.s_end ? e : a.s_end;
+  } else {
+    return a.s_end;
+  }
+}
+template <bool RAGGED>
+__device__ __forceinline__ int slot_data(const TreeArgs &a, int slot, int u) {
+  if (u < a.B) return u;
+  if constexpr (RAGGED) return a.pad_standin[slot];
+  else return 0;
+}
+
+template <int W, bool RAGGED = false>
 __device__ __forceinline__ bool block_has_work(const TreeArgs &a) {
   if (a.skip_claims && (int64_t)*a.skip_claims > a.skip_cap) return false;
+  if constexpr (RAGGED) {
+    if (a.block_end[blockIdx.x] <= a.s_begin) return false;  // (its utterances ended in an earlier launch)
+  }
   if (a.order) {
     bool any = false;
 #pragma unroll
@@ -238,7 +263,7 @@ __device__ __forceinline__ bool block_has_work(const TreeArgs &a) {
 // Wave-uniform.  Decided before the body loads any state, so that each variant's body (a whole
 // copy: tree_synth_body) has live ranges of its own: with the branch between time loops instead,
 // the register allocator spilled 160-250 VGPRs of the persistent state to scratch.
-template <int W>
+template <int W, bool RAGGED = false>
 __device__ __forceinline__ int noise_variant(const TreeArgs &a, int g = -1, int gl = -1) {
   constexpr int UPB_ = Geom<W>::UPB;
   if (g < 0) {
@@ -247,9 +272,10 @@ __device__ __forceinline__ int noise_variant(const TreeArgs &a, int g = -1, int 
   }
   const int slot = blockIdx.x * UPB_ + g;
   const int u = a.order ? a.order[slot] : slot;
-  const int ue = u < a.B ? u : 0;  // (a padding slot runs utterance 0's data and stores nothing)
+  // (a padding slot runs utterance 0's data -- ragged calls: a live utterance's of its block -- and stores nothing)
+  const int ue = slot_data<RAGGED>(a, slot, u);
   const int64_t row = a.frame_row ? a.frame_row[ue] : ue;
-  const int64_t nh = (a.s_end - 1) / a.hop - a.s_begin / a.hop + 1;
+  const int64_t nh = (block_s_end<RAGGED>(a) - 1) / a.hop - a.s_begin / a.hop + 1;  // (ragged calls: the block's own hops only)
   const PlanHop *h0 = a.hops + row * a.hop_stride;
   uint64_t m = 0;
   for (int64_t q = gl; q < nh; q += W) m |= h0[q].noise;
@@ -304,7 +330,7 @@ template <bool TAPS> using TapWindowT = std::conditional_t<TAPS, TapWindow, NoTa
 // gl's kind and inputs for the hop and evaluates the word at every sample; a mixed hop's samples
 // read their dense records as without HOPS.
 // TAPS: the launch's signal taps collected after each sample (TapWindow); no tap code otherwise.
-template <bool PROF, int MODEL, bool HOPS, int W, int NZ, bool TAPS = false>
+template <bool PROF, int MODEL, bool HOPS, int W, int NZ, bool TAPS = false, bool RAGGED = false>
 __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
   constexpr int UPB_ = Geom<W>::UPB, WPB_ = Geom<W>::WPB;
   const int lane = threadIdx.x;  // 0 .. 64 WPB - 1
@@ -312,7 +338,7 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
   const int slot = blockIdx.x * UPB_ + g;
   const int u = a.order ? a.order[slot] : slot;
   const bool valid = u < a.B;
-  const int ue = valid ? u : 0;
+  const int ue = slot_data<RAGGED>(a, slot, u);
   double *X = lds.X[g];
   const Tables &T = *a.tab;
   {  // stage the hot tables (8-byte words; Consts is a multiple of 8 bytes)
@@ -334,7 +360,7 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
   // this utterance's plan records, word gl % 16 of each (tree_plan.h)
   const uint64_t *pl = a.plan + row * a.plan_stride * PLAN_WORDS + (gl & (PLAN_WORDS - 1));
   const int hop = a.hop;
-  const int64_t n = a.s_end - a.s_begin;
+  const int64_t n = block_s_end<RAGGED>(a) - a.s_begin;  // (ragged calls: the block's utterances may end before s_end)
   int k = (int)(a.s_begin / hop) + 1, i = (int)(a.s_begin % hop);
   // The output stage (dU/dt, Chebyshev low-pass, scaling) and the glottal-tone filter do not feed
   // back into the tube: the kernel stores the radiated flows and section 25's pressures, and K6
@@ -455,17 +481,17 @@ __device__ __forceinline__ void tree_synth_run(const TreeArgs &a, WaveLdsT<W> &l
 // -1.7 %, profiles/r05f_variant_order_ab.txt.)
 // (TAPS: the full noise phases only -- the variants give the same values, and each would be one
 // more copy of the body to compile)
-template <bool PROF, int MODEL, bool HOPS = false, int W = TW, bool TAPS = false>
+template <bool PROF, int MODEL, bool HOPS = false, int W = TW, bool TAPS = false, bool RAGGED = false>
 __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &lds, uint64_t *prof) {
-  if (!block_has_work<W>(a)) return;
+  if (!block_has_work<W, RAGGED>(a)) return;
   if constexpr (TAPS) {
-    tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL, true>(a, lds, prof);
+    tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL, true, RAGGED>(a, lds, prof);
   } else if constexpr (HOPS) {
-    with_noise_variant(noise_variant<W>(a), [&](auto V) {
-      tree_synth_run<PROF, MODEL, HOPS, W, decltype(V)::value>(a, lds, prof);
+    with_noise_variant(noise_variant<W, RAGGED>(a), [&](auto V) {
+      tree_synth_run<PROF, MODEL, HOPS, W, decltype(V)::value, false, RAGGED>(a, lds, prof);
     });
   } else {
-    tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL>(a, lds, prof);
+    tree_synth_run<PROF, MODEL, HOPS, W, NZ_FULL, false, RAGGED>(a, lds, prof);
   }
 }
 
@@ -479,7 +505,7 @@ __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &
 // slots' state, so the pair's kernel must fit 256 registers per lane.
 // ---------------------------------------------------------------------------
 // (W = 64: the voice kernel's pairs, one utterance per workgroup of two waves, tree_pair64_body)
-template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW, bool TAPS = false>
+template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW, bool TAPS = false, bool RAGGED = false>
 __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &lds, int grp, uint64_t *prof = nullptr) {
   constexpr int UPB_ = Geom<W>::UPB;
   constexpr int NT = 2 * 64 * Geom<W>::WPB;  // threads per workgroup (a pair per wave of the one-wave kernel)
@@ -489,7 +515,7 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
   const int slot = blockIdx.x * UPB_ + g;
   const int u = a.order ? a.order[slot] : slot;
   const bool valid = u < a.B;
-  const int ue = valid ? u : 0;
+  const int ue = slot_data<RAGGED>(a, slot, u);
   double *X = lds.X[g];
   const Tables &T = *a.tab;
   {
@@ -511,7 +537,7 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
   double *p25o = a.p25 + (int64_t)ue * a.p25_stride;
   const uint64_t *pl = a.plan + row * a.plan_stride * PLAN_WORDS + (gl & (PLAN_WORDS - 1));
   const int hop = a.hop;
-  const int64_t n = a.s_end - a.s_begin;
+  const int64_t n = block_s_end<RAGGED>(a) - a.s_begin;  // (ragged calls: the block's utterances may end before s_end)
   int k = (int)(a.s_begin / hop) + 1, i = (int)(a.s_begin % hop);
   if constexpr (ROLE == ROLE_DYN) frame_load<W>(gl, R, X, fu + (k - 1), fu + k);
   const PlanHop *hr = HOPS ? a.hops + row * a.hop_stride : nullptr;
@@ -652,10 +678,10 @@ __device__ unsigned int pair_cu_slots[2048];
 // SIMD would share its issue slots.  When a workgroup's four waves do not sit on four SIMDs, by the
 // wave index.  Any placement gives a valid pairing; this only balances the SIMDs (against roles by
 // the wave index, the wave slot's or the block's parity: profiles/r06_pair_ab.txt).
-template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false>
+template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false, bool RAGGED = false>
 __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &lds, int *pattern,
                                                uint64_t *prof = nullptr) {
-  if (!block_has_work<TW>(a)) return;
+  if (!block_has_work<TW, RAGGED>(a)) return;
   const int wave = (int)threadIdx.x / 64;
   int grp, st;
   unsigned int *cu_word = nullptr;
@@ -687,16 +713,16 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
   }
   const bool stat = st != 0;
   if (!stat) {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, TW, TAPS>(a, lds, grp, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, TW, TAPS, RAGGED>(a, lds, grp, prof);
   } else if constexpr (TAPS) {  // (the full noise phases only: tree_synth_body)
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, TW, true>(a, lds, grp, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, TW, true, RAGGED>(a, lds, grp, prof);
   } else if constexpr (HOPS) {
     const int g = grp * Geom<TW>::UPW + ((int)threadIdx.x % 64) / TW, gl = (int)threadIdx.x % TW;
-    with_noise_variant(noise_variant<TW>(a, g, gl), [&](auto V) {
-      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF>(a, lds, grp, prof);
+    with_noise_variant(noise_variant<TW, RAGGED>(a, g, gl), [&](auto V) {
+      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF, TW, false, RAGGED>(a, lds, grp, prof);
     });
   } else {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF>(a, lds, grp, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, TW, false, RAGGED>(a, lds, grp, prof);
   }
   if (threadIdx.x == 0 && cu_bit) atomicAnd(cu_word, ~cu_bit);  // (after the run's last workgroup barrier)
 }
@@ -704,20 +730,20 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
 // The voice kernel's pairs (64 lanes per utterance): one utterance per workgroup of two waves, wave 0
 // DYN and wave 1 STAT, for batches that leave a SIMD to each wave (afs_tree.h TREE_PAIR64_MAX): the
 // sample's chain split over two SIMDs instead of one wave's.
-template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false>
+template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false, bool RAGGED = false>
 __device__ __forceinline__ void tree_pair64_body(const TreeArgs &a, WaveLdsT<64> &lds, uint64_t *prof = nullptr) {
-  if (!block_has_work<64>(a)) return;
+  if (!block_has_work<64, RAGGED>(a)) return;
   const bool stat = threadIdx.x >= 64;
   if (!stat) {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, 64, TAPS>(a, lds, 0, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_DYN, PROF, 64, TAPS, RAGGED>(a, lds, 0, prof);
   } else if constexpr (TAPS) {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64, true>(a, lds, 0, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64, true, RAGGED>(a, lds, 0, prof);
   } else if constexpr (HOPS) {
-    with_noise_variant(noise_variant<64>(a, 0, (int)threadIdx.x % 64), [&](auto V) {
-      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
+    with_noise_variant(noise_variant<64, RAGGED>(a, 0, (int)threadIdx.x % 64), [&](auto V) {
+      tree_pair_run<MODEL, HOPS, decltype(V)::value, ROLE_STAT, PROF, 64, false, RAGGED>(a, lds, 0, prof);
     });
   } else {
-    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64>(a, lds, 0, prof);
+    tree_pair_run<MODEL, HOPS, NZ_FULL, ROLE_STAT, PROF, 64, false, RAGGED>(a, lds, 0, prof);
   }
 }
 

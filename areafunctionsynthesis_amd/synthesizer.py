@@ -174,6 +174,74 @@ class Context:
                      "nonfinite": nonfinite},)
         return res if len(res) > 1 else res[0]
 
+    def synthesize_ragged(self, frames, num_frames, hop: int, seeds=None, out=None, report: bool = False,
+                          nonfinite=None, taps=False, taps_out=None):
+        """:meth:`synthesize` for utterances of different lengths in one call (tree solver).
+        ``frames``: a ``[B, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[B, Fmax, 1072]`` of which
+        utterance u plays the first ``num_frames[u]`` frames (the rest is never read), or a list of
+        per-utterance FRAME_DTYPE arrays (``num_frames=None``: their lengths), which is padded.
+        Returns ``(audio[B, out_stride], lengths[B])`` with ``lengths[u] = (num_frames[u]-1)*hop``
+        valid samples in row u -- ``out_stride`` is the longest utterance's, or the row length of a
+        given ``out`` -- then the taps ``[B, n_taps, out_stride]`` and the report as :meth:`synthesize`
+        appends them.  Row u is bit for bit ``synthesize(frames[u:u+1, :num_frames[u]], hop)`` with
+        its seed.  Nothing is written past a row's end: an ``out`` allocated here is zero there."""
+        if isinstance(frames, (list, tuple)):
+            rows = [np.ascontiguousarray(f, dtype=FRAME_DTYPE).reshape(-1) for f in frames]
+            if num_frames is None:
+                num_frames = [len(r) for r in rows]
+            padded = np.zeros((len(rows), max(len(r) for r in rows)), dtype=FRAME_DTYPE)
+            for u, r in enumerate(rows):
+                padded[u, : len(r)] = r
+            frames = padded
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != FRAME_DTYPE or frames.ndim != 2:
+                raise ValueError("frames must be a 2-D FRAME_DTYPE array [B, Fmax]")
+            B, fstride = frames.shape
+            frames = np.ascontiguousarray(frames)
+        else:
+            B, fstride = int(frames.shape[0]), int(frames.shape[1])
+            if _nbytes(frames) != B * fstride * FRAME_DTYPE.itemsize:
+                raise ValueError("device frames must hold B*Fmax*1072 bytes")
+        counts = None
+        if num_frames is not None:  # (a host array: the library builds the launch layout from it)
+            counts = np.ascontiguousarray(num_frames, dtype=np.int32)
+            if counts.shape != (B,):
+                raise ValueError("num_frames must hold B counts")
+        lengths = None if counts is None else (counts.astype(np.int64) - 1) * hop
+        if seeds is None:
+            seeds = np.arange(1, B + 1, dtype=np.uint32)
+        if isinstance(seeds, np.ndarray):
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if out is None:
+            out = np.zeros((B, max(int(lengths.max()), 0) if lengths is not None else 0), dtype=np.float64)
+        if tuple(out.shape)[:1] != (B,) or len(out.shape) != 2:
+            raise ValueError("out must be [B, out_stride] doubles")
+        ostride = int(out.shape[1])
+        if _nbytes(out) != B * ostride * 8:
+            raise ValueError("out must be [B, out_stride] doubles")
+        if nonfinite is None and report:
+            nonfinite = np.zeros(B, dtype=np.uint8)
+        if nonfinite is not None and _nbytes(nonfinite) != B:
+            raise ValueError("nonfinite must hold B bytes")
+        if taps:
+            nt = getattr(self, "n_taps", 0)
+            if taps_out is None:
+                taps_out = np.zeros((B, nt, ostride), dtype=np.float64)
+            if nt and _nbytes(taps_out) != B * nt * ostride * 8:  # (no taps set: the library refuses the call)
+                raise ValueError("taps_out must hold B*n_taps*out_stride doubles")
+        rep = _native.AfsReport()
+        st = self._lib.afs_synthesize_ragged(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                             _vp(_addr(seeds)), B, hop, _vp(_addr(out)), ostride,
+                                             _vp(_addr(taps_out) if taps else 0), _vp(_addr(nonfinite)),
+                                             ctypes.byref(rep) if report else None)
+        _native.check(st, self._h, "afs_synthesize_ragged")
+        res = (out, lengths) + ((taps_out,) if taps else ())
+        if report:
+            res += ({"device_ms": rep.device_ms, "samples": rep.samples,
+                     "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                     "nonfinite": nonfinite},)
+        return res
+
     def noise_plans(self, frames: np.ndarray, hop: int, s_begin: int = 0, s_end: Optional[int] = None) -> np.ndarray:
         """Diagnostics (tree solver): the noise-source plan records K5 computes for samples
         [s_begin, s_end) of frames[rows, F] -> uint64[rows, s_end - s_begin, AFS_PLAN_WORDS]."""

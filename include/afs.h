@@ -217,6 +217,24 @@ afs_status afs_synchronize(afs_ctx *ctx);
 afs_status afs_synthesize(afs_ctx *ctx, const afs_frame *frames, const uint32_t *seeds,
                           int32_t batch, int32_t num_frames, int32_t hop, double *out,
                           uint8_t *nonfinite, afs_report *report);
+/* afs_synthesize for utterances of different lengths.  frames[batch][frame_stride]; utterance u plays
+ * frames 0 .. num_frames[u]-1 and produces T_u = (num_frames[u]-1)*hop samples into
+ * out[u*out_stride .. +T_u).  num_frames is a HOST array (the launch layout is built from it without a
+ * read-back), 2 <= num_frames[u] <= frame_stride; out_stride >= max T_u.  Frames at or past
+ * num_frames[u] are never read and samples at or past T_u are never written.  taps_out: NULL, or
+ * [batch][n_taps][out_stride] with the context's tap list (afs_set_taps).  Row u, its tap rows, its
+ * rand() count (afs_rng_draws) and its non-finite flag are bit for bit those of afs_synthesize /
+ * afs_synthesize_taps called on utterance u alone with its own num_frames (same lane width).
+ * report->samples = sum of T_u.  Tree solver only (else AFS_ERR_UNSUPPORTED).
+ * frames, seeds, out, taps_out and nonfinite may be host or device memory and AFS_ASYNC treats them
+ * as in afs_synthesize (a host out or taps_out is staged: uploaded, written up to each row's end and
+ * copied back whole).  AFS_ERR_INVALID_ARGUMENT: a count outside 2..frame_stride, out_stride below
+ * the longest T_u, a NULL num_frames, taps_out without a tap list.  Utterances of one length share
+ * K1's workgroups; each distinct length costs at most one partly filled workgroup. */
+afs_status afs_synthesize_ragged(afs_ctx *ctx, const afs_frame *frames, int64_t frame_stride,
+                                 const int32_t *num_frames, const uint32_t *seeds, int32_t batch, int32_t hop,
+                                 double *out, int64_t out_stride, double *taps_out,
+                                 uint8_t *nonfinite, afs_report *report);
 /* Diagnostics: the number of rand() calls (TdsModel.cpp:1690-1692) each utterance of the last
  * afs_synthesize / afs_play_target_sequences call made, draws[batch] (host or device).  A
  * count that differs from the reference's means a noise source switched on or off at a
