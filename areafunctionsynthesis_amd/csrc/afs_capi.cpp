@@ -60,20 +60,8 @@ int lanes_for(const afs_ctx *c, int64_t B) {
   return B <= c->simds ? TREE_VOICE_W : TREE_W;
 }
 
-afs_status ensure(afs_ctx *c, void **buf, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return AFS_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  HIP_TRY(c, hipMalloc(buf, bytes));
-  *cap = bytes;
-  if (std::find(c->grown.begin(), c->grown.end(), buf) == c->grown.end()) c->grown.push_back(buf);
-  return AFS_OK;
-}
-
 }  // namespace afs
 
-using afs::ensure;
 using afs::fail;
 using afs::is_device_ptr;
 using afs::lanes_for;
@@ -143,27 +131,31 @@ SlotOrder plain_order(const afs_ctx *c) {
 // audio to out[u * ostride + s], the state the launches carry between them (the context's or a
 // session's), and K1's slot order.
 struct SynthCall {
-  const afs_frame *frames;
-  int64_t fstride;
-  int rows, ntrans, hop;
-  double *out;
-  int64_t ostride;
-  void *ws;
-  int32_t *rng;
-  void *lanes;
-  int64_t bp;
-  int B, width;
-  const int32_t *frame_row;
+  const afs_frame *frames = nullptr;
+  int64_t fstride = 0;
+  int rows = 0, ntrans = 0, hop = 0;
+  double *out = nullptr;
+  int64_t ostride = 0;
+  void *ws = nullptr;
+  int32_t *rng = nullptr;
+  void *lanes = nullptr;
+  int64_t bp = 0;
+  int B = 0, width = 0;
+  const int32_t *frame_row = nullptr;
   SlotOrder so;
-  // the _taps calls: tap k of utterance u to taps[(u * n_taps + k) * tstride + s] (null: no taps)
-  double *taps = nullptr;
-  int64_t tstride = 0;
+  // the _taps calls: tap k of utterance u to out[(u * n_taps + k) * stride + s] (null: no taps)
+  struct Taps {
+    double *out = nullptr;
+    int64_t stride = 0;
+  } taps;
   // afs_synthesize_ragged (device arrays; null: every utterance plays all ntrans transitions):
   // utterance u plays row_hops[u] of them, ntrans the longest's; block_end and pad_standin belong to
   // the slot order so.order (afs_ragged_order.h)
-  const int32_t *row_hops = nullptr;
-  const int64_t *block_end = nullptr;
-  const int32_t *pad_standin = nullptr;
+  struct Ragged {
+    const int32_t *row_hops = nullptr;
+    const int64_t *block_end = nullptr;
+    const int32_t *pad_standin = nullptr;
+  } ragged;
 };
 
 // the context's tap list as K1 reads it: a current from the slot the solver leaves it in, a
@@ -197,20 +189,27 @@ struct LaunchPlans {
 // line-aligned window (tree_kernel.h).
 afs_status p25_for(afs_ctx *c, const SynthCall &call, int64_t per, int64_t *stride) {
   *stride = per + ((call.ostride - per) % 16 + 16) % 16;
-  return ensure(c, &c->p25, &c->p25_bytes, ((size_t)call.B * (size_t)*stride + 32) * sizeof(double));
+  HIP_TRY(c, c->p25.reserve(((size_t)call.B * (size_t)*stride + 32) * sizeof(double)));
+  return AFS_OK;
 }
 // the p25 base for the launch whose outputs start at `out`
 double *p25_row0(const afs_ctx *c, const double *out) {
   const int64_t want = (int64_t)((reinterpret_cast<uintptr_t>(out) >> 3) & 15);
-  const int64_t have = (int64_t)((reinterpret_cast<uintptr_t>(c->p25) >> 3) & 15);
-  return (double *)c->p25 + ((want - have) % 16 + 16) % 16;
+  const int64_t have = (int64_t)((reinterpret_cast<uintptr_t>(c->p25.data()) >> 3) & 15);
+  return c->p25.as<double>() + ((want - have) % 16 + 16) % 16;
 }
 
 // K5's arguments for samples [s0, s1) of the call's frame rows, dense records into `plan`
 afs::PlanArgs plan_args(const afs_ctx *c, const afs_frame *frames, int64_t fstride, int rows, int hop, int64_t s0,
                         int64_t s1, uint64_t *plan, int64_t plan_stride) {
-  return afs::PlanArgs{c->dev_tab, frames, fstride, rows, hop, s0, s1, plan, plan_stride,
-                       c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0, c->dev_tab->consts.sec};
+  afs::PlanArgs pa{};
+  pa.tab = c->tab(), pa.uo = c->tab()->consts.sec;
+  pa.frames = frames, pa.frame_stride = fstride;
+  pa.rows = rows, pa.hop = hop;
+  pa.s_begin = s0, pa.s_end = s1;
+  pa.plan = plan, pa.plan_stride = plan_stride;
+  pa.two_mass = c->cfg.options.glottis_model == AFS_GLOTTIS_TWO_MASS ? 1 : 0;
+  return pa;
 }
 
 // K1 over samples [s0, s1) of the call, then K6 over them (both timed).
@@ -218,30 +217,37 @@ afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, in
                                int64_t p25_stride) {
   const SlotOrder &so = call.so;
   double *out = call.out + s0, *p25 = p25_row0(c, out);
-  afs::TreeArgs a{c->dev_tab, call.frames, call.fstride, call.frame_row, call.hop, s0, s1, out, call.ostride, lp.plan,
-                  lp.plan_stride, call.lanes, (double *)call.ws, call.B, c->host_tab.uni, lp.hops, lp.hop_stride, p25,
-                  p25_stride, so.order, so.variants ? 1 : 0, so.grid, so.variants_dev, lp.skip, lp.skip_cap};
+  afs::TreeArgs a{};
+  a.tab = c->tab(), a.uni = c->host_tab.uni;
+  a.frames = call.frames, a.frame_stride = call.fstride, a.frame_row = call.frame_row;
+  a.hop = call.hop, a.s_begin = s0, a.s_end = s1;
+  a.out = out, a.out_stride = call.ostride;
+  a.plan = lp.plan, a.plan_stride = lp.plan_stride;
+  a.hops = lp.hops, a.hop_stride = lp.hop_stride;
+  a.skip_claims = lp.skip, a.skip_cap = lp.skip_cap;
+  a.lane_state = call.lanes, a.lds_state = (double *)call.ws, a.B = call.B;
+  a.p25 = p25, a.p25_stride = p25_stride;
+  a.order = so.order, a.grid_blocks = so.grid;
+  a.noise_variants = so.variants ? 1 : 0, a.variants_dev = so.variants_dev;
   {  // the pairs' STAT priority mode by the launch's rounds of workgroups per CU slot (two per CU):
      // mode 2 from two rounds, 0 below (profiles/r06_pair_ab.txt r06zh-r06zm)
     const int64_t blocks = so.grid > 0 ? so.grid : ((int64_t)call.B + afs::TREE_UPB - 1) / afs::TREE_UPB;
     const int64_t slots = std::max<int64_t>(1, c->simds / 2), rounds = (blocks + slots - 1) / slots;
     a.stat_prio = (call.width == afs::TREE_W && rounds >= 2) ? 2 : 0;
   }
-  if (call.taps) {  // (every launch of the call carries the list: the rows go on where the last launch stopped)
+  if (call.taps.out) {  // (every launch of the call carries the list: the rows go on where the last launch stopped)
     a.taps = tap_set(c);
-    a.tap_out = call.taps + s0;
-    a.tap_stride = call.tstride;
+    a.tap_out = call.taps.out + s0, a.tap_stride = call.taps.stride;
   }
-  a.block_end = call.block_end;
-  a.pad_standin = call.pad_standin;
+  a.block_end = call.ragged.block_end, a.pad_standin = call.ragged.pad_standin;
   hipEvent_t e1 = prof_event(c);
   HIP_TRY(c, afs::launch_tree_synth(a, call.width, c->stream));
   hipEvent_t e2 = prof_event(c);
   prof_pair(c, e1, e2, 0);
   // K6: the glottal-tone filter and the output stage of the launch's samples
-  HIP_TRY(c, afs::launch_tree_output(c->dev_tab, (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
+  HIP_TRY(c, afs::launch_tree_output(c->tab(), (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
                                      c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap,
-                                     call.row_hops, call.hop, s0));
+                                     call.ragged.row_hops, call.hop, s0));
   prof_pair(c, e2, prof_event(c), 2);
   return AFS_OK;
 }
@@ -251,10 +257,9 @@ bool hop_mode(const afs_ctx *c, int hop) { return !c->plan_dense && hop >= afs::
 
 // The hop records and K5's work list for `rows` rows of `hstride` hop slots.
 afs_status ensure_hop_buffers(afs_ctx *c, int rows, int64_t hstride) {
-  const size_t hbytes = (size_t)rows * (size_t)hstride * sizeof(afs::tree::PlanHop);
-  afs_status st = ensure(c, &c->hops, &c->hops_bytes, hbytes);
-  if (st != AFS_OK) return st;
-  return ensure(c, &c->plan_work, &c->plan_work_bytes, (size_t)afs::plan_work_bytes(rows, hstride));
+  HIP_TRY(c, c->hops.reserve((size_t)rows * (size_t)hstride * sizeof(afs::tree::PlanHop)));
+  HIP_TRY(c, c->plan_work.reserve((size_t)afs::plan_work_bytes(rows, hstride)));
+  return AFS_OK;
 }
 
 // Hop mode's fast path: K5 decides every hop of the call first -- one record per (row, hop), the
@@ -276,14 +281,14 @@ afs_status run_hop_call(afs_ctx *c, const SynthCall &call, bool *done) {
   if (!hop_mode(c, hop) || hbytes > c->plan_budget) return AFS_OK;
   afs_status st;
   if ((st = ensure_hop_buffers(c, rows, hstride)) != AFS_OK) return st;
-  afs::tree::PlanHop *hbuf = (afs::tree::PlanHop *)c->hops;
-  uint32_t *work = (uint32_t *)c->plan_work;
+  afs::tree::PlanHop *hbuf = c->hops.as<afs::tree::PlanHop>();
+  uint32_t *work = c->plan_work.as<uint32_t>();
   afs::PlanArgs pa = plan_args(c, call.frames, call.fstride, rows, hop, 0, S, nullptr, 0);
   pa.hops = hbuf;
   pa.hop_stride = hstride;
   pa.work = work;
   pa.compact = true;
-  pa.row_hops = call.row_hops;
+  pa.row_hops = call.ragged.row_hops;
   hipEvent_t e0 = prof_event(c);
   HIP_TRY(c, afs::launch_plan_hops_iv(pa, c->stream));
   // Slots for the mixed hops: one for every hop of the call when they fit the budget (small calls:
@@ -297,13 +302,13 @@ afs_status run_hop_call(afs_ctx *c, const SynthCall &call, bool *done) {
   const int64_t every = (int64_t)rows * hstride;
   const bool small = every * slot_bytes <= std::min<int64_t>(c->plan_budget, SMALL_CALL_DENSE_BYTES);
   const int64_t cap = small ? every : std::min<int64_t>(every, std::max<int64_t>(1, c->plan_budget / slot_bytes));
-  if ((st = ensure(c, &c->plan, &c->plan_bytes, (size_t)(cap * slot_bytes))) != AFS_OK) return st;
-  pa.plan = (uint64_t *)c->plan;
+  HIP_TRY(c, c->plan.reserve((size_t)(cap * slot_bytes)));
+  pa.plan = c->plan.as<uint64_t>();
   pa.dense_cap = cap;
   HIP_TRY(c, afs::launch_plan_hops_wave(pa, c->stream));
   const bool guard = cap < every;
   if (guard) {
-    HIP_TRY(c, hipMemcpyAsync(c->hcount, work + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hcount.data(), work + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_k5, c->stream));
   }
   prof_pair(c, e0, prof_event(c), 1);
@@ -311,13 +316,13 @@ afs_status run_hop_call(afs_ctx *c, const SynthCall &call, bool *done) {
   int64_t p25_stride = 0;
   if ((st = p25_for(c, call, per, &p25_stride)) != AFS_OK) return st;
   for (int64_t s0 = 0; s0 < S; s0 += per) {
-    const LaunchPlans lp{(const uint64_t *)c->plan, 0, hbuf + s0 / hop, hstride, guard ? work + 1 : nullptr, cap};
+    const LaunchPlans lp{c->plan.as<uint64_t>(), 0, hbuf + s0 / hop, hstride, guard ? work + 1 : nullptr, cap};
     if ((st = launch_synth_output(c, call, s0, std::min(S, s0 + per), lp, p25_stride)) != AFS_OK) return st;
   }
   if (guard) {
     HIP_TRY(c, hipEventSynchronize(c->ev_k5));
     // (overflow: the guarded launches did nothing, the state is still the call's initial state)
-    if ((int64_t)(uint32_t)*c->hcount > cap) return AFS_OK;
+    if ((int64_t)*c->hcount.as<uint32_t>() > cap) return AFS_OK;
   }
   *done = true;
   return AFS_OK;
@@ -348,24 +353,24 @@ afs_status run_chunked(afs_ctx *c, const SynthCall &call) {
   const int64_t hstride = afs::plan_hop_slots(0, per, hop) + 1;
   const size_t pbytes = (size_t)rows * (size_t)(hops ? hstride * hop : per) * afs::PLAN_RECORD_BYTES;
   afs_status st;
-  if ((st = ensure(c, &c->plan, &c->plan_bytes, pbytes)) != AFS_OK) return st;
+  HIP_TRY(c, c->plan.reserve(pbytes));
   if (hops && (st = ensure_hop_buffers(c, rows, hstride)) != AFS_OK) return st;
   int64_t p25_stride = 0;
   if ((st = p25_for(c, call, per, &p25_stride)) != AFS_OK) return st;
-  afs::tree::PlanHop *hbuf = hops ? (afs::tree::PlanHop *)c->hops : nullptr;
+  afs::tree::PlanHop *hbuf = hops ? c->hops.as<afs::tree::PlanHop>() : nullptr;
   for (int64_t s0 = 0; s0 < S; s0 += per) {
     const int64_t s1 = std::min(S, s0 + per);
-    afs::PlanArgs pa = plan_args(c, call.frames, call.fstride, rows, hop, s0, s1, (uint64_t *)c->plan, per);
+    afs::PlanArgs pa = plan_args(c, call.frames, call.fstride, rows, hop, s0, s1, c->plan.as<uint64_t>(), per);
     pa.hops = hbuf;
     pa.hop_stride = hstride;
-    pa.work = hops ? (uint32_t *)c->plan_work : nullptr;
+    pa.work = hops ? c->plan_work.as<uint32_t>() : nullptr;
     pa.compact = hops;
     pa.dense_cap = (int64_t)rows * hstride;  // (hop mode: a slot for every hop of the chunk)
-    pa.row_hops = call.row_hops;
+    pa.row_hops = call.ragged.row_hops;
     hipEvent_t e0 = prof_event(c);
     HIP_TRY(c, hops ? afs::launch_plan_hops(pa, c->stream) : afs::launch_plan(pa, c->stream));
     prof_pair(c, e0, prof_event(c), 1);
-    const LaunchPlans lp{(const uint64_t *)c->plan, per, hbuf, hstride};
+    const LaunchPlans lp{c->plan.as<uint64_t>(), per, hbuf, hstride};
     if ((st = launch_synth_output(c, call, s0, s1, lp, p25_stride)) != AFS_OK) return st;
   }
   return AFS_OK;
@@ -376,9 +381,12 @@ afs_status run_lane(afs_ctx *c, const SynthCall &call) {
   const int per = (int)std::max<int64_t>(1, 8192 / std::max(1, call.hop));
   for (int k = 1; k <= call.ntrans; k += per) {
     const int ke = std::min(call.ntrans + 1, k + per);
-    double *o = call.out + (int64_t)(k - 1) * call.hop;
-    afs::LaneArgs a{c->dev_tab, call.frames, call.fstride, call.frame_row, k, ke, call.hop, o, call.ostride,
-                    (double *)call.ws, call.rng, call.bp, call.B, c->cfg.solver == AFS_SOLVER_SOR ? 1 : 0};
+    afs::LaneArgs a{};
+    a.tab = c->tab(), a.sor = c->cfg.solver == AFS_SOLVER_SOR ? 1 : 0;
+    a.frames = call.frames, a.frame_stride = call.fstride, a.frame_row = call.frame_row;
+    a.k_begin = k, a.k_end = ke, a.hop = call.hop;
+    a.out = call.out + (int64_t)(k - 1) * call.hop, a.out_stride = call.ostride;
+    a.ws = (double *)call.ws, a.rng = call.rng, a.bp = call.bp, a.B = call.B;
     hipEvent_t e0 = prof_event(c);
     HIP_TRY(c, afs::launch_lane_synth(a, c->stream));
     prof_pair(c, e0, prof_event(c), 0);
@@ -414,6 +422,45 @@ afs_status reset_state(afs_ctx *c, void *ws, int32_t *rng, void *lanes, int64_t 
   return AFS_OK;
 }
 
+// ---- call staging: the host-or-device arguments of the calls, the context's state, the report ----
+
+// An argument of a call that may live on the host.  `dev` is what the kernels read or write: the
+// caller's array `user` when that is device memory (or null), else (`host`) a buffer of the context
+// sized to its bytes, which an input is uploaded to (`upload`) and an output is copied back from.
+// An output whose kernels write only part of it is uploaded first as well: the rest is the caller's.
+template <class T>
+struct Staged {
+  T *user = nullptr, *dev = nullptr;
+  size_t bytes = 0;
+  bool host = false;
+  afs_status stage(afs_ctx *c, T *p, size_t n, afs::DeviceBuf &buf, bool upload = false) {
+    user = dev = p;
+    bytes = n;
+    host = p && !is_device_ptr(p);
+    if (!host) return AFS_OK;
+    HIP_TRY(c, buf.reserve(n));
+    dev = buf.as<T>();
+    if (upload) HIP_TRY(c, hipMemcpyAsync(buf.data(), p, n, hipMemcpyHostToDevice, c->stream));
+    return AFS_OK;
+  }
+  // queue the copy a host output is owed (to `to`, a pinned stand-in for the caller's array, when given)
+  afs_status copy_back(afs_ctx *c, void *to = nullptr) const {
+    if (host) HIP_TRY(c, hipMemcpyAsync(to ? to : user, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    return AFS_OK;
+  }
+};
+
+// frames[n] on the device: a host array is uploaded through the context's staging buffer
+using Frames = Staged<const afs_frame>;
+afs_status frames_to_device(afs_ctx *c, const afs_frame *frames, size_t n, Frames *d) {
+  return d->stage(c, frames, n * sizeof(afs_frame), c->stage_in, true);
+}
+// seeds[B] on the device likewise (null stays null: the reset kernels seed utterance u with u + 1)
+using Seeds = Staged<const uint32_t>;
+afs_status seeds_to_device(afs_ctx *c, const uint32_t *seeds, int B, Seeds *d) {
+  return d->stage(c, seeds, (size_t)B * sizeof(uint32_t), c->stage_seeds, true);
+}
+
 // Per-utterance non-finite flags (into `flags`, a host or device array of B bytes, or nowhere)
 // and their count (into the pinned c->hcount, read after the stream synchronises).  *host_sync
 // is set when the flags go to host memory (the call must synchronise before returning).
@@ -421,73 +468,37 @@ afs_status nonfinite_report(afs_ctx *c, void *ws, int64_t bp, int B, uint8_t *fl
                             bool *host_sync) {
   *host_sync = false;
   if (!flags && !want_count) return AFS_OK;
-  uint8_t *dflags = flags;
-  if (flags && !is_device_ptr(flags)) {
-    afs_status s = ensure(c, &c->stage_nf, &c->stage_nf_bytes, (size_t)B);
-    if (s != AFS_OK) return s;
-    dflags = (uint8_t *)c->stage_nf;
-    *host_sync = true;
-  }
-  HIP_TRY(c, hipMemsetAsync(c->dcount, 0, sizeof(int32_t), c->stream));
+  Staged<uint8_t> f;
+  afs_status s = f.stage(c, flags, (size_t)B, c->stage_nf);
+  if (s != AFS_OK) return s;
+  *host_sync = f.host;
+  int32_t *dcount = c->dcount.as<int32_t>();
+  HIP_TRY(c, hipMemsetAsync(dcount, 0, sizeof(int32_t), c->stream));
   if (tree(c))
-    HIP_TRY(c, afs::launch_tree_nonfinite((const double *)ws, B, c->dcount, dflags, c->stream));
+    HIP_TRY(c, afs::launch_tree_nonfinite((const double *)ws, B, dcount, f.dev, c->stream));
   else
-    HIP_TRY(c, afs::launch_lane_nonfinite((const double *)ws, bp, B, c->dcount, dflags, c->stream));
-  if (*host_sync) HIP_TRY(c, hipMemcpyAsync(flags, dflags, (size_t)B, hipMemcpyDeviceToHost, c->stream));
-  if (want_count) HIP_TRY(c, hipMemcpyAsync(c->hcount, c->dcount, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, afs::launch_lane_nonfinite((const double *)ws, bp, B, dcount, f.dev, c->stream));
+  if ((s = f.copy_back(c)) != AFS_OK) return s;
+  if (want_count) HIP_TRY(c, hipMemcpyAsync(c->hcount.data(), dcount, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   return AFS_OK;
 }
 
-// ---- call staging: the host-or-device arguments of the calls, the context's state, the report ----
-
-// `p` when it is device memory; else (*host set) the context's buffer *buf grown to `bytes`, which
-// the caller copies to or from.
-template <class T>
-afs_status device_or_stage(afs_ctx *c, T *p, size_t bytes, void **buf, size_t *cap, T **d, bool *host) {
-  *d = p;
-  *host = !is_device_ptr(p);
-  if (!*host) return AFS_OK;
-  const afs_status s = ensure(c, buf, cap, bytes);
-  *d = (T *)*buf;
-  return s;
-}
-
-// frames[n] on the device: a host array is uploaded through the context's staging buffer
-afs_status frames_to_device(afs_ctx *c, const afs_frame *frames, size_t n, const afs_frame **d) {
-  const size_t bytes = n * sizeof(afs_frame);
-  bool host;
-  const afs_status s = device_or_stage(c, frames, bytes, &c->stage_in, &c->stage_in_bytes, d, &host);
-  if (s != AFS_OK) return s;
-  if (host) HIP_TRY(c, hipMemcpyAsync(c->stage_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
-  return AFS_OK;
-}
-
-// seeds[B] on the device likewise (null stays null: the reset kernels seed utterance u with u + 1)
-afs_status seeds_to_device(afs_ctx *c, const uint32_t *seeds, int B, const uint32_t **d) {
-  *d = nullptr;
-  if (!seeds) return AFS_OK;
-  const size_t bytes = (size_t)B * sizeof(uint32_t);
-  bool host;
-  const afs_status s = device_or_stage(c, seeds, bytes, &c->stage_seeds, &c->stage_seeds_bytes, d, &host);
-  if (s != AFS_OK) return s;
-  if (host) HIP_TRY(c, hipMemcpyAsync(c->stage_seeds, seeds, bytes, hipMemcpyHostToDevice, c->stream));
-  return AFS_OK;
-}
-
-// where the kernels write out[n]: `out` itself, or the context's staging buffer for a host array
-afs_status device_out(afs_ctx *c, double *out, size_t n, double **d, bool *host) {
-  return device_or_stage(c, out, n * sizeof(double), &c->stage_out, &c->stage_out_bytes, d, host);
-}
-
-// the context's state buffers for B utterances of `width` lanes, grown as needed and reset to the seeds
+// the context's state buffers for B utterances of `width` lanes, enlarged as needed and reset to the seeds
 afs_status fresh_state(afs_ctx *c, int B, int width, const uint32_t *dseeds) {
   const int64_t bp = pad64(B);
-  afs_status s;
-  if ((s = ensure(c, &c->ws, &c->ws_bytes, ws_bytes_for(c, bp))) != AFS_OK) return s;
-  if ((s = ensure(c, (void **)&c->rng, &c->rng_bytes, (size_t)(32 * bp) * sizeof(int32_t))) != AFS_OK) return s;
-  if (tree(c) && (s = ensure(c, &c->tree_lanes, &c->tree_lanes_bytes, lanes_bytes_for(c, bp, width))) != AFS_OK)
-    return s;
-  return reset_state(c, c->ws, c->rng, c->tree_lanes, bp, B, dseeds, width);
+  HIP_TRY(c, c->ws.reserve(ws_bytes_for(c, bp)));
+  HIP_TRY(c, c->rng.reserve((size_t)(32 * bp) * sizeof(int32_t)));
+  if (tree(c)) HIP_TRY(c, c->tree_lanes.reserve(lanes_bytes_for(c, bp, width)));
+  return reset_state(c, c->ws.data(), c->rng.as<int32_t>(), c->tree_lanes.data(), bp, B, dseeds, width);
+}
+
+// the call on the context's state (fresh_state) for B utterances of `width` lanes
+SynthCall context_call(const afs_ctx *c, int B, int width) {
+  SynthCall call;
+  call.ws = c->ws.data(), call.rng = c->rng.as<int32_t>(), call.lanes = c->tree_lanes.data();
+  call.bp = pad64(B), call.B = B, call.width = width;
+  call.so = plain_order(c);
+  return call;
 }
 
 // the report of a call whose kernels ran between ev0 and ev1 (after the stream has synchronised)
@@ -497,41 +508,38 @@ afs_status fill_report(afs_ctx *c, afs_report *rep, int64_t samples) {
   HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   rep->device_ms = ms;
   rep->samples = samples;
-  rep->nonfinite_utterances = *c->hcount;
+  rep->nonfinite_utterances = *c->hcount.as<int32_t>();
   rep->kernel = c->cfg.solver;
   return AFS_OK;
 }
 
-// The end of a whole-trajectory call on the context's state: ev1, the non-finite flags and count, the
-// copy of staged audio to a host `out`, then the wait and the report.  The call returns without a
-// wait only when it is asynchronous (`async`) and nothing goes to host memory: no host `out`, no
-// report, no host flags.  `elems`: the doubles of out (rows and their stride); `samples`: what the
-// report counts.
-afs_status finish_call(afs_ctx *c, int B, int64_t elems, int64_t samples, double *out, const double *dout,
-                       bool host_out, uint8_t *nonfinite, afs_report *rep, bool async) {
+// The end of a whole-trajectory call on the context's state: the copy of staged taps to a host
+// array, ev1, the non-finite flags and count, the copy of staged audio to a host `out`, then the wait
+// and the report.  The call returns without a wait only when it is asynchronous (`async`) and nothing
+// goes to host memory: no host `out` or taps, no report, no host flags.  `samples`: what the report
+// counts.
+afs_status finish_call(afs_ctx *c, int B, int64_t samples, const Staged<double> &out, const Staged<double> &taps,
+                       uint8_t *nonfinite, afs_report *rep, bool async) {
+  afs_status s;
+  if ((s = taps.copy_back(c)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   c->last_B = B;
   bool nf_sync = false;
-  afs_status s = nonfinite_report(c, c->ws, pad64(B), B, nonfinite, rep != nullptr, &nf_sync);
-  if (s != AFS_OK) return s;
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (!async || host_out || rep || nf_sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((s = nonfinite_report(c, c->ws.data(), pad64(B), B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return s;
+  if ((s = out.copy_back(c)) != AFS_OK) return s;
+  if (!async || out.host || taps.host || rep || nf_sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
   return fill_report(c, rep, samples);
 }
 
 afs_status draws_of(afs_ctx *c, const void *ws, int B, int64_t *draws) {
   if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "rand() call counts are kept by the tree solver only");
-  int64_t *d = draws;
-  void *tmp = nullptr;
-  if (!is_device_ptr(draws)) {
-    HIP_TRY(c, hipMalloc(&tmp, (size_t)B * sizeof(int64_t)));
-    d = (int64_t *)tmp;
-  }
-  hipError_t e = afs::launch_tree_draws((const double *)ws, B, d, c->stream);
-  if (e == hipSuccess && tmp) e = hipMemcpyAsync(draws, d, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (tmp) (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(c, AFS_ERR_HIP, "afs_rng_draws: %s", hipGetErrorString(e));
+  afs::DeviceBuf tmp;
+  Staged<int64_t> d;
+  afs_status s;
+  if ((s = d.stage(c, draws, (size_t)B * sizeof(int64_t), tmp)) != AFS_OK) return s;
+  HIP_TRY(c, afs::launch_tree_draws((const double *)ws, B, d.dev, c->stream));
+  if ((s = d.copy_back(c)) != AFS_OK) return s;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
 
@@ -589,13 +597,12 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
   afs::build_tables(&ctx->host_tab, c.sampling_rate_hz, c.options);
   if (ctx->host_tab.n_rounds <= 0) { afs_destroy(ctx); return AFS_ERR_UNSUPPORTED; }
   auto bail = [&](afs_status s) { afs_destroy(ctx); return s; };
-  if (hipMalloc((void **)&ctx->dev_tab, sizeof(afs::Tables)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
-  if (hipMemcpy(ctx->dev_tab, &ctx->host_tab, sizeof(afs::Tables), hipMemcpyHostToDevice) != hipSuccess)
+  if (ctx->dev_tab.reserve(sizeof(afs::Tables)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
+  if (hipMemcpy(ctx->dev_tab.data(), &ctx->host_tab, sizeof(afs::Tables), hipMemcpyHostToDevice) != hipSuccess)
     return bail(AFS_ERR_HIP);
-  if (hipMalloc((void **)&ctx->dcount, sizeof(int32_t)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
-  if (hipHostMalloc((void **)&ctx->hcount, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-    return bail(AFS_ERR_OUT_OF_MEMORY);
-  *ctx->hcount = 0;
+  if (ctx->dcount.reserve(sizeof(int32_t)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
+  if (ctx->hcount.reserve(sizeof(int32_t)) != hipSuccess) return bail(AFS_ERR_OUT_OF_MEMORY);
+  *ctx->hcount.as<int32_t>() = 0;
   if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) return bail(AFS_ERR_HIP);
   // the code objects of the kernels a synthesis call launches, loaded now rather than at their
   // first launch (which cost a real-time caller's first buffer ~35 ms)
@@ -622,16 +629,10 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
 void afs_destroy(afs_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
-  for (void **buf : c->grown)  // (every buffer of the context that ensure() allocated)
-    if (*buf) (void)hipFree(*buf);
-  if (c->dev_tab) (void)hipFree(c->dev_tab);
-  if (c->dcount) (void)hipFree(c->dcount);
-  if (c->hcount) (void)hipHostFree(c->hcount);
-  if (c->ragged_host) (void)hipHostFree(c->ragged_host);
   for (hipEvent_t e : {c->ev_k5, c->ev_ragged, c->ev0, c->ev1})
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
-  delete c;
+  delete c;  // (its buffers go with it: afs_buf.h)
 }
 
 const char *afs_last_error(const afs_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -676,24 +677,24 @@ static afs_status shape_order(afs_ctx *c, const afs_frame *dframes, int64_t fstr
   const int upb = afs::TREE_UPB;
   if (!tree(c) || !c->shape_order || width == afs::TREE_VOICE_W || B <= upb) return AFS_OK;
   const int nb = (B + upb - 1) / upb;
-  afs_status s;
   // keys[B], sorted keys[B], indices[B], the variant flag
   const size_t kb = (size_t)B * (2 * sizeof(uint64_t) + sizeof(int32_t)) + 16;
-  if ((s = ensure(c, &c->keys, &c->keys_bytes, kb)) != AFS_OK) return s;
-  uint64_t *dkeys = (uint64_t *)c->keys, *dsorted = dkeys + B;
+  HIP_TRY(c, c->keys.reserve(kb));
+  uint64_t *dkeys = c->keys.as<uint64_t>(), *dsorted = dkeys + B;
   int32_t *didx = (int32_t *)(dsorted + B), *dvar = didx + B;
   HIP_TRY(c, afs::launch_utterance_keys(dframes, fstride, B, dkeys, c->stream));
   const int64_t waves_per_simd = (int64_t)B / ((int64_t)(64 / afs::TREE_W) * std::max(1, c->simds));
   const int mode = c->noise_variants == 0 ? 0 : c->noise_variants == 1 ? 1 : 2;
-  if ((s = ensure(c, &c->order_buf, &c->order_bytes, (size_t)nb * upb * sizeof(int32_t))) != AFS_OK) return s;
+  HIP_TRY(c, c->order_buf.reserve((size_t)nb * upb * sizeof(int32_t)));
+  int32_t *dorder = c->order_buf.as<int32_t>();
   size_t tb = 0;  // (the first call asks for the sort's scratch size only)
   HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, mode, waves_per_simd >= 16, dvar,
-                                    (int32_t *)c->order_buf, nb * upb, nullptr, &tb, c->stream));
-  if ((s = ensure(c, &c->sort_tmp, &c->sort_tmp_bytes, tb + 256)) != AFS_OK) return s;
-  tb = c->sort_tmp_bytes;
+                                    dorder, nb * upb, nullptr, &tb, c->stream));
+  HIP_TRY(c, c->sort_tmp.reserve(tb + 256));
+  tb = c->sort_tmp.capacity();
   HIP_TRY(c, afs::launch_slot_order(dkeys, dsorted, didx, B, mode, waves_per_simd >= 16, dvar,
-                                    (int32_t *)c->order_buf, nb * upb, c->sort_tmp, &tb, c->stream));
-  so->order = (const int32_t *)c->order_buf;
+                                    dorder, nb * upb, c->sort_tmp.data(), &tb, c->stream));
+  so->order = dorder;
   so->grid = nb;
   so->variants_dev = dvar;
   return AFS_OK;
@@ -707,43 +708,6 @@ static afs_status taps_check(afs_ctx *c, const char *fn, const double *taps_out)
   return AFS_OK;
 }
 
-// afs_synthesize; force_async: leave the stream running unless a host buffer needs a wait;
-// taps_out: afs_synthesize_taps (the context's taps beside the audio), else null
-static afs_status synth_core(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
-                             int32_t hop, double *out, uint8_t *nonfinite, afs_report *rep, bool force_async,
-                             int lanes = 0, double *taps_out = nullptr) {
-  if (!frames || !out || B <= 0 || F < 2 || hop < 1)
-    return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  const int64_t T = (int64_t)(F - 1) * hop;
-  double *dtaps = nullptr;
-  bool host_taps = false;
-  const size_t taps_bytes = (size_t)B * (size_t)c->n_taps * (size_t)T * sizeof(double);
-  afs_status s;
-  const afs_frame *dframes;
-  const uint32_t *dseeds;
-  double *dout;
-  bool host_out;
-  if ((s = frames_to_device(c, frames, (size_t)B * F, &dframes)) != AFS_OK) return s;
-  if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
-  if ((s = device_out(c, out, (size_t)B * T, &dout, &host_out)) != AFS_OK) return s;
-  const int width = lanes > 0 ? lanes : lanes_for(c, B);
-  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
-  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  if (taps_out && (s = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps,
-                                       &host_taps)) != AFS_OK)
-    return s;
-  SynthCall call{dframes, F, B, F - 1, hop, dout, T, c->ws, c->rng, c->tree_lanes, pad64(B), B, width, nullptr, {}};
-  call.taps = dtaps;
-  call.tstride = T;
-  if ((s = shape_order(c, dframes, F, B, width, &call.so)) != AFS_OK) return s;
-  if ((s = run_call(c, call)) != AFS_OK) return s;
-  // (a host taps_out is copied back as a host out is, and the call then waits)
-  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
-  const bool async = (force_async || (c->cfg.flags & AFS_ASYNC)) && !host_taps;
-  return finish_call(c, B, (int64_t)B * T, (int64_t)B * T, out, dout, host_out, nonfinite, rep, async);
-}
-
 // The launch layout of a ragged call and its per-row hop counts on the device: built on the host from
 // num_frames (afs_ragged_order.h), packed into the context's pinned buffer and uploaded on the stream
 // -- no host wait, except for the previous ragged call's upload when that has not been read yet.
@@ -754,16 +718,9 @@ static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, in
   const size_t bytes = end_bytes + 2 * slot_bytes + (size_t)B * sizeof(int32_t);
   if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
   else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
-  if (bytes > c->ragged_host_bytes) {
-    if (c->ragged_host) (void)hipHostFree(c->ragged_host);
-    c->ragged_host = nullptr;
-    c->ragged_host_bytes = 0;
-    HIP_TRY(c, hipHostMalloc(&c->ragged_host, bytes, hipHostMallocDefault));
-    c->ragged_host_bytes = bytes;
-  }
-  const afs_status s = ensure(c, &c->ragged, &c->ragged_bytes, bytes);
-  if (s != AFS_OK) return s;
-  char *h = (char *)c->ragged_host, *d = (char *)c->ragged;
+  HIP_TRY(c, c->ragged_host.reserve(bytes));
+  HIP_TRY(c, c->ragged.reserve(bytes));
+  char *h = c->ragged_host.as<char>(), *d = c->ragged.as<char>();
   std::memcpy(h, ro.block_end.data(), end_bytes);
   std::memcpy(h + end_bytes, ro.order.data(), slot_bytes);
   std::memcpy(h + end_bytes + slot_bytes, ro.standin.data(), slot_bytes);
@@ -771,77 +728,87 @@ static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, in
   for (int u = 0; u < B; ++u) hops[u] = num_frames[u] - 1;
   HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
-  call->block_end = (const int64_t *)d;
+  call->ragged.block_end = (const int64_t *)d;
   call->so.order = (const int32_t *)(d + end_bytes);
   call->so.grid = ro.grid;
-  call->pad_standin = (const int32_t *)(d + end_bytes + slot_bytes);
-  call->row_hops = (const int32_t *)(d + end_bytes + 2 * slot_bytes);
+  call->ragged.pad_standin = (const int32_t *)(d + end_bytes + slot_bytes);
+  call->ragged.row_hops = (const int32_t *)(d + end_bytes + 2 * slot_bytes);
   return AFS_OK;
 }
 
-// afs_synthesize_ragged: synth_core for utterances of different lengths.  One call of ntrans = the
-// longest utterance's transitions; K1's blocks each hold one length and end their time loop there
-// (ragged_layout), K5 and K6 stop at each row's own end.  The slot order by shape inside a length
-// group is left out.
-static afs_status synth_ragged(afs_ctx *c, const afs_frame *frames, int64_t fstride, const int32_t *num_frames,
-                               const uint32_t *seeds, int32_t B, int32_t hop, double *out, int64_t ostride,
-                               double *taps_out, uint8_t *nonfinite, afs_report *rep) {
-  const char *fn = "afs_synthesize_ragged";
-  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
-  if (!frames || !out || B <= 0 || hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, out, batch>0, hop>=1", fn);
-  if (!num_frames || is_device_ptr(num_frames))
-    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
-  int32_t Fmax = 0;
-  int64_t total = 0;
-  for (int32_t u = 0; u < B; ++u) {
-    const int32_t F = num_frames[u];
-    if (F < 2 || F > fstride)
-      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 2..frame_stride = %lld", fn, u, F,
-                  (long long)fstride);
-    Fmax = std::max(Fmax, F);
-    total += (int64_t)(F - 1) * hop;
-  }
-  const int64_t Tmax = (int64_t)(Fmax - 1) * hop;
-  if (ostride < Tmax)
-    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out_stride %lld below the longest utterance's %lld samples", fn,
-                (long long)ostride, (long long)Tmax);
-  if (taps_out && c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
+// A whole-trajectory call on fresh state of the context, as its entry point has validated it:
+// afs_synthesize (with taps_out: afs_synthesize_taps), or with num_frames afs_synthesize_ragged, the
+// same call for utterances of different lengths.
+struct Trajectories {
+  const afs_frame *frames = nullptr;  // frames[u * fstride + k]
+  int64_t fstride = 0;
+  const int32_t *num_frames = nullptr;  // ragged: the frames of each utterance (host); null: F each
+  int32_t F = 0;                        // the frames of the longest utterance
+  const uint32_t *seeds = nullptr;
+  int32_t B = 0, hop = 0;
+  double *out = nullptr;  // out[u * ostride + s]
+  int64_t ostride = 0;
+  double *taps_out = nullptr;  // the context's taps beside the audio, rows of ostride as well (null: none)
+  int64_t samples = 0;         // what the report counts
+  bool force_async = false;    // leave the stream running unless a host buffer needs a wait
+  int lanes = 0;               // the tree kernel's lanes per utterance (0: chosen for B)
+};
+
+// Everything between an entry point's validation and finish_call.  The uniform call takes K1's slot
+// order from shape_order.  The ragged call is one call of ntrans = the longest utterance's
+// transitions: K1's blocks each hold one length and end their time loop there (ragged_layout), K5 and
+// K6 stop at each row's own end; the slot order by shape inside a length group is left out
+// (DESIGN.md 2.8).
+static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfinite, afs_report *rep) {
   HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int B = t.B;
+  const bool ragged = t.num_frames != nullptr;
+  const size_t out_bytes = (size_t)B * (size_t)t.ostride * sizeof(double), taps_bytes = out_bytes * (size_t)c->n_taps;
   afs_status s;
-  const afs_frame *dframes;
-  const uint32_t *dseeds;
-  double *dout, *dtaps = nullptr;
-  bool host_out, host_taps = false;
-  const size_t out_bytes = (size_t)B * (size_t)ostride * sizeof(double), taps_bytes = out_bytes * (size_t)c->n_taps;
-  if ((s = frames_to_device(c, frames, (size_t)B * (size_t)fstride, &dframes)) != AFS_OK) return s;
-  if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
-  if ((s = device_out(c, out, (size_t)B * (size_t)ostride, &dout, &host_out)) != AFS_OK) return s;
-  // (a host out goes up first and comes back whole: what lies past each row's end is the caller's)
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(dout, out, out_bytes, hipMemcpyHostToDevice, c->stream));
-  const int width = lanes_for(c, B);
-  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
+  Frames fr;
+  Seeds seeds;
+  Staged<double> out, taps;
+  if ((s = frames_to_device(c, t.frames, (size_t)B * (size_t)t.fstride, &fr)) != AFS_OK) return s;
+  if ((s = seeds_to_device(c, t.seeds, B, &seeds)) != AFS_OK) return s;
+  // (a ragged call's host out and taps go up first and come back whole: what lies past each row's
+  // end is the caller's)
+  if ((s = out.stage(c, t.out, out_bytes, c->stage_out, ragged)) != AFS_OK) return s;
+  const int width = t.lanes > 0 ? t.lanes : lanes_for(c, B);
+  if ((s = fresh_state(c, B, width, seeds.dev)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  if (taps_out) {
-    if ((s = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps, &host_taps)) != AFS_OK)
-      return s;
-    if (host_taps) HIP_TRY(c, hipMemcpyAsync(dtaps, taps_out, taps_bytes, hipMemcpyHostToDevice, c->stream));
-  }
-  SynthCall call{dframes, fstride, B, Fmax - 1, hop, dout, ostride, c->ws, c->rng, c->tree_lanes, pad64(B), B, width,
-                 nullptr, plain_order(c)};
-  call.taps = dtaps;
-  call.tstride = ostride;
-  if ((s = ragged_layout(c, num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, hop, &call)) != AFS_OK) return s;
+  if ((s = taps.stage(c, t.taps_out, taps_bytes, c->stage_taps, ragged)) != AFS_OK) return s;
+  SynthCall call = context_call(c, B, width);
+  call.frames = fr.dev, call.fstride = t.fstride, call.rows = B;
+  call.ntrans = t.F - 1, call.hop = t.hop;
+  call.out = out.dev, call.ostride = t.ostride;
+  call.taps.out = taps.dev, call.taps.stride = t.ostride;
+  s = ragged ? ragged_layout(c, t.num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, t.hop, &call)
+             : shape_order(c, fr.dev, t.fstride, B, width, &call.so);
+  if (s != AFS_OK) return s;
   if ((s = run_call(c, call)) != AFS_OK) return s;
-  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
-  const bool async = (c->cfg.flags & AFS_ASYNC) && !host_taps;
-  return finish_call(c, B, (int64_t)B * ostride, total, out, dout, host_out, nonfinite, rep, async);
+  return finish_call(c, B, t.samples, out, taps, nonfinite, rep, t.force_async || (c->cfg.flags & AFS_ASYNC));
+}
+
+// afs_synthesize: every utterance F frames, rows of T = (F - 1) * hop samples
+static afs_status synth_uniform(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
+                                int32_t hop, double *out, double *taps_out, uint8_t *nonfinite, afs_report *rep,
+                                bool force_async, int lanes) {
+  if (!frames || !out || B <= 0 || F < 2 || hop < 1)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
+  Trajectories t;
+  t.frames = frames, t.fstride = t.F = F;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.out = out, t.ostride = (int64_t)(F - 1) * hop, t.taps_out = taps_out;
+  t.samples = (int64_t)B * t.ostride;
+  t.force_async = force_async, t.lanes = lanes;
+  return synth_core(c, t, nonfinite, rep);
 }
 
 afs_status afs::synthesize_async(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
                                  int32_t hop, double *out, uint8_t *nonfinite, int lanes) {
   if (lanes != 0 && lanes != afs::TREE_W && lanes != afs::TREE_VOICE_W)
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "synthesize: %d lanes per utterance", lanes);
-  return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, nullptr, true, lanes);
+  return synth_uniform(c, frames, seeds, B, F, hop, out, nullptr, nonfinite, nullptr, true, lanes);
 }
 
 extern "C" {
@@ -849,9 +816,7 @@ extern "C" {
 afs_status afs_synthesize(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B,
                           int32_t F, int32_t hop, double *out, uint8_t *nonfinite, afs_report *rep) {
   if (!c) return AFS_ERR_INVALID_ARGUMENT;
-  if (!frames || !out || B <= 0 || F < 2 || hop < 1)
-    return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_synthesize: need frames, out, batch>0, num_frames>=2, hop>=1");
-  return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, rep, false);
+  return synth_uniform(c, frames, seeds, B, F, hop, out, nullptr, nonfinite, rep, false, 0);
 }
 
 afs_status afs_set_taps(afs_ctx *c, const afs_tap *taps, int32_t n) {
@@ -874,14 +839,36 @@ afs_status afs_synthesize_taps(afs_ctx *c, const afs_frame *frames, const uint32
   if (!c) return AFS_ERR_INVALID_ARGUMENT;
   const afs_status s = taps_check(c, "afs_synthesize_taps", taps_out);
   if (s != AFS_OK) return s;
-  return synth_core(c, frames, seeds, B, F, hop, out, nonfinite, rep, false, 0, taps_out);
+  return synth_uniform(c, frames, seeds, B, F, hop, out, taps_out, nonfinite, rep, false, 0);
 }
 
-afs_status afs_synthesize_ragged(afs_ctx *c, const afs_frame *frames, int64_t frame_stride, const int32_t *num_frames,
-                                 const uint32_t *seeds, int32_t B, int32_t hop, double *out, int64_t out_stride,
+afs_status afs_synthesize_ragged(afs_ctx *c, const afs_frame *frames, int64_t fstride, const int32_t *num_frames,
+                                 const uint32_t *seeds, int32_t B, int32_t hop, double *out, int64_t ostride,
                                  double *taps_out, uint8_t *nonfinite, afs_report *rep) {
   if (!c) return AFS_ERR_INVALID_ARGUMENT;
-  return synth_ragged(c, frames, frame_stride, num_frames, seeds, B, hop, out, out_stride, taps_out, nonfinite, rep);
+  const char *fn = "afs_synthesize_ragged";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!frames || !out || B <= 0 || hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, out, batch>0, hop>=1", fn);
+  if (!num_frames || is_device_ptr(num_frames))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
+  Trajectories t;
+  for (int32_t u = 0; u < B; ++u) {
+    const int32_t F = num_frames[u];
+    if (F < 2 || F > fstride)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 2..frame_stride = %lld", fn, u, F,
+                  (long long)fstride);
+    t.F = std::max(t.F, F);
+    t.samples += (int64_t)(F - 1) * hop;
+  }
+  const int64_t Tmax = (int64_t)(t.F - 1) * hop;
+  if (ostride < Tmax)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out_stride %lld below the longest utterance's %lld samples", fn,
+                (long long)ostride, (long long)Tmax);
+  if (taps_out && c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
+  t.frames = frames, t.fstride = fstride, t.num_frames = num_frames;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.out = out, t.ostride = ostride, t.taps_out = taps_out;
+  return synth_core(c, t, nonfinite, rep);
 }
 
 afs_status afs_section_currents(int32_t section, int32_t *in, int32_t out[2]) {
@@ -942,10 +929,10 @@ afs_status afs_kernel_times(afs_ctx *c, double *synth_ms, int32_t *synth_launche
 
 afs_status afs_rng_draws(afs_ctx *c, int32_t B, int64_t *draws) {
   if (!c) return AFS_ERR_INVALID_ARGUMENT;
-  if (!draws || B <= 0 || B != c->last_B || !c->ws)
+  if (!draws || B <= 0 || B != c->last_B || !c->ws.data())
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_rng_draws: need draws[B] with B = the last call's batch");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  return draws_of(c, c->ws, B, draws);
+  return draws_of(c, c->ws.data(), B, draws);
 }
 
 afs_status afs_noise_plans(afs_ctx *c, const afs_frame *frames, int32_t rows, int32_t F, int32_t hop, int64_t s0,
@@ -958,15 +945,14 @@ afs_status afs_noise_plans(afs_ctx *c, const afs_frame *frames, int32_t rows, in
                                              "0 <= s_begin < s_end <= (num_frames-1)*hop");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   afs_status s;
-  const afs_frame *dframes;
-  if ((s = frames_to_device(c, frames, (size_t)rows * F, &dframes)) != AFS_OK) return s;
+  Frames fr;
+  if ((s = frames_to_device(c, frames, (size_t)rows * F, &fr)) != AFS_OK) return s;
   const int64_t n = s1 - s0;
   const size_t bytes = (size_t)rows * (size_t)n * afs::PLAN_RECORD_BYTES;
-  uint64_t *dplans;
-  bool host_out;
-  if ((s = device_or_stage(c, plans, bytes, &c->plan, &c->plan_bytes, &dplans, &host_out)) != AFS_OK) return s;
-  HIP_TRY(c, afs::launch_plan(plan_args(c, dframes, F, rows, hop, s0, s1, dplans, n), c->stream));
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(plans, dplans, bytes, hipMemcpyDeviceToHost, c->stream));
+  Staged<uint64_t> out;
+  if ((s = out.stage(c, plans, bytes, c->plan)) != AFS_OK) return s;
+  HIP_TRY(c, afs::launch_plan(plan_args(c, fr.dev, F, rows, hop, s0, s1, out.dev, n), c->stream));
+  if ((s = out.copy_back(c)) != AFS_OK) return s;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
@@ -983,27 +969,24 @@ afs_status afs_noise_plan_hops(afs_ctx *c, const afs_frame *frames, int32_t rows
                                              "0 <= s_begin < s_end <= (num_frames-1)*hop");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   afs_status s;
-  const afs_frame *dframes;
-  if ((s = frames_to_device(c, frames, (size_t)rows * F, &dframes)) != AFS_OK) return s;
+  Frames fr;
+  if ((s = frames_to_device(c, frames, (size_t)rows * F, &fr)) != AFS_OK) return s;
   const int64_t n = s1 - s0, slots = afs::plan_hop_slots(s0, s1, hop);
   const size_t pbytes = (size_t)rows * (size_t)n * afs::PLAN_RECORD_BYTES;
   const size_t hbytes = (size_t)rows * (size_t)slots * sizeof(afs::tree::PlanHop);
-  uint64_t *dplans;
-  uint8_t *dhops;
-  bool host_plans, host_hops;
-  if ((s = device_or_stage(c, plans, pbytes, &c->plan, &c->plan_bytes, &dplans, &host_plans)) != AFS_OK) return s;
-  // (the records of the samples outside mixed hops are left as the caller passed them)
-  if (host_plans) HIP_TRY(c, hipMemcpyAsync(dplans, plans, pbytes, hipMemcpyHostToDevice, c->stream));
-  if ((s = device_or_stage(c, hops, hbytes, &c->hops, &c->hops_bytes, &dhops, &host_hops)) != AFS_OK) return s;
-  if ((s = ensure(c, &c->plan_work, &c->plan_work_bytes, (size_t)afs::plan_work_bytes(rows, slots))) != AFS_OK)
-    return s;
-  afs::PlanArgs pa = plan_args(c, dframes, F, rows, hop, s0, s1, dplans, n);
-  pa.hops = (afs::tree::PlanHop *)dhops;
+  Staged<uint64_t> out_plans;
+  Staged<uint8_t> out_hops;
+  // (uploaded first: the records of the samples outside mixed hops are left as the caller passed them)
+  if ((s = out_plans.stage(c, plans, pbytes, c->plan, true)) != AFS_OK) return s;
+  if ((s = out_hops.stage(c, hops, hbytes, c->hops)) != AFS_OK) return s;
+  HIP_TRY(c, c->plan_work.reserve((size_t)afs::plan_work_bytes(rows, slots)));
+  afs::PlanArgs pa = plan_args(c, fr.dev, F, rows, hop, s0, s1, out_plans.dev, n);
+  pa.hops = (afs::tree::PlanHop *)out_hops.dev;
   pa.hop_stride = slots;
-  pa.work = (uint32_t *)c->plan_work;
+  pa.work = c->plan_work.as<uint32_t>();
   HIP_TRY(c, afs::launch_plan_hops(pa, c->stream));
-  if (host_plans) HIP_TRY(c, hipMemcpyAsync(plans, dplans, pbytes, hipMemcpyDeviceToHost, c->stream));
-  if (host_hops) HIP_TRY(c, hipMemcpyAsync(hops, dhops, hbytes, hipMemcpyDeviceToHost, c->stream));
+  if ((s = out_plans.copy_back(c)) != AFS_OK) return s;
+  if ((s = out_hops.copy_back(c)) != AFS_OK) return s;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
@@ -1015,17 +998,15 @@ afs_status afs_plan_hop_words(afs_ctx *c, const uint8_t *hops, const double *rat
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_plan_hop_words: need hops, ratio, words, n>0");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t hb = (size_t)n * sizeof(afs::tree::PlanHop), rb = (size_t)n * 8, wb = (size_t)n * AFS_PLAN_WORDS * 8;
-  char *d = nullptr;
-  HIP_TRY(c, hipMalloc((void **)&d, hb + rb + wb));
-  hipError_t e = hipMemcpyAsync(d, hops, hb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + hb, ratio, rb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = afs::launch_tree_hop_words((const afs::tree::PlanHop *)d, (const double *)(d + hb), n, (uint64_t *)(d + hb + rb),
-                                   c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(words, d + hb + rb, wb, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  HIP_TRY(c, e);
+  afs::DeviceBuf tmp;
+  HIP_TRY(c, tmp.reserve(hb + rb + wb));
+  char *d = tmp.as<char>();
+  HIP_TRY(c, hipMemcpyAsync(d, hops, hb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d + hb, ratio, rb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, afs::launch_tree_hop_words((const afs::tree::PlanHop *)d, (const double *)(d + hb), n,
+                                        (uint64_t *)(d + hb + rb), c->stream));
+  HIP_TRY(c, hipMemcpyAsync(words, d + hb + rb, wb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
 
@@ -1037,20 +1018,19 @@ afs_status afs_tube_interpolate(afs_ctx *c, const afs_frame *fl, const afs_frame
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_tube_interpolate: need left, right, ratio, area, length, n>0");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t fb = (size_t)n * sizeof(afs_frame), rb = (size_t)n * 8, ob = (size_t)n * AFS_NUM_TUBE_SECTIONS * 8;
-  char *d = nullptr;
-  HIP_TRY(c, hipMalloc((void **)&d, 2 * fb + rb + 2 * ob));
+  afs::DeviceBuf tmp;
+  HIP_TRY(c, tmp.reserve(2 * fb + rb + 2 * ob));
+  char *d = tmp.as<char>();
   afs_frame *dl = (afs_frame *)d, *dr = (afs_frame *)(d + fb);
   double *dratio = (double *)(d + 2 * fb), *da = (double *)(d + 2 * fb + rb), *dlen = (double *)(d + 2 * fb + rb + ob);
-  hipError_t e = hipMemcpyAsync(dl, fl, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dr, fr, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dratio, ratio, rb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(da, 0, 2 * ob, c->stream);
-  if (e == hipSuccess) e = afs::launch_tree_interp(c->dev_tab, dl, dr, dratio, n, da, dlen, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(area, da, ob, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(length, dlen, ob, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  HIP_TRY(c, e);
+  HIP_TRY(c, hipMemcpyAsync(dl, fl, fb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dr, fr, fb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dratio, ratio, rb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(da, 0, 2 * ob, c->stream));
+  HIP_TRY(c, afs::launch_tree_interp(c->tab(), dl, dr, dratio, n, da, dlen, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(area, da, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(length, dlen, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
 
@@ -1063,17 +1043,16 @@ afs_status afs_session_create(afs_ctx *c, int32_t B, const uint32_t *seeds, afs_
   s->bp = pad64(B);
   s->lanes = lanes_for(c, B);  // (fixed for the session: the per-lane state layout depends on it)
   auto bail = [&](hipError_t e) {
-    afs_session_destroy(s);
+    delete s;
     return fail(c, e == hipErrorOutOfMemory ? AFS_ERR_OUT_OF_MEMORY : AFS_ERR_HIP, "session alloc: %s", hipGetErrorString(e));
   };
   hipError_t e;
-  if ((e = hipMalloc(&s->ws, ws_bytes_for(c, s->bp))) != hipSuccess) return bail(e);
-  if ((e = hipMalloc((void **)&s->rng, (size_t)(32 * s->bp) * sizeof(int32_t))) != hipSuccess) return bail(e);
-  if (tree(c) && (e = hipMalloc(&s->tree_lanes, lanes_bytes_for(c, s->bp, s->lanes))) != hipSuccess) return bail(e);
-  if ((e = hipMalloc((void **)&s->pair, (size_t)B * 2 * sizeof(afs_frame))) != hipSuccess) return bail(e);
-  if ((e = hipMalloc((void **)&s->seeds, (size_t)B * sizeof(uint32_t))) != hipSuccess) return bail(e);
-  if ((e = hipHostMalloc((void **)&s->hframes, (size_t)B * sizeof(afs_frame), hipHostMallocDefault)) != hipSuccess)
-    return bail(e);
+  if ((e = s->ws.reserve(ws_bytes_for(c, s->bp))) != hipSuccess) return bail(e);
+  if ((e = s->rng.reserve((size_t)(32 * s->bp) * sizeof(int32_t))) != hipSuccess) return bail(e);
+  if (tree(c) && (e = s->tree_lanes.reserve(lanes_bytes_for(c, s->bp, s->lanes))) != hipSuccess) return bail(e);
+  if ((e = s->pair.reserve((size_t)B * 2 * sizeof(afs_frame))) != hipSuccess) return bail(e);
+  if ((e = s->seeds.reserve((size_t)B * sizeof(uint32_t))) != hipSuccess) return bail(e);
+  if ((e = s->hframes.reserve((size_t)B * sizeof(afs_frame))) != hipSuccess) return bail(e);
   *out = s;
   afs_status st = afs_session_reset(s, seeds);
   if (st != AFS_OK) {
@@ -1089,10 +1068,11 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds) {
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   if (seeds) {
     hipMemcpyKind k = is_device_ptr(seeds) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIP_TRY(c, hipMemcpyAsync(s->seeds, seeds, (size_t)s->B * 4, k, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(s->seeds.data(), seeds, (size_t)s->B * 4, k, c->stream));
   }
   // (no seeds: the reset kernels seed voice u with u + 1)
-  afs_status st = reset_state(c, s->ws, s->rng, s->tree_lanes, s->bp, s->B, seeds ? s->seeds : nullptr, s->lanes);
+  afs_status st = reset_state(c, s->ws.data(), s->rng.as<int32_t>(), s->tree_lanes.data(), s->bp, s->B,
+                              seeds ? s->seeds.as<uint32_t>() : nullptr, s->lanes);
   if (st != AFS_OK) return st;
   s->latched = false;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1100,14 +1080,6 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds) {
 }
 
 void afs_session_destroy(afs_session *s) {
-  if (!s) return;
-  if (s->ws) (void)hipFree(s->ws);
-  if (s->rng) (void)hipFree(s->rng);
-  if (s->tree_lanes) (void)hipFree(s->tree_lanes);
-  if (s->pair) (void)hipFree(s->pair);
-  if (s->seeds) (void)hipFree(s->seeds);
-  if (s->hframes) (void)hipHostFree(s->hframes);
-  if (s->hout) (void)hipHostFree(s->hout);
   delete s;
 }
 
@@ -1125,13 +1097,14 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   const bool in_dev = is_device_ptr(frames);
   const afs_frame *src = frames;
   if (!in_dev) {  // host frames: through the session's pinned buffer
-    std::memcpy(s->hframes, frames, (size_t)B * sizeof(afs_frame));
-    src = s->hframes;
+    std::memcpy(s->hframes.data(), frames, (size_t)B * sizeof(afs_frame));
+    src = s->hframes.as<afs_frame>();
   }
   const hipMemcpyKind k = in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   // frames[u] -> pair[u][slot]
   const int slot = s->latched ? 1 : 0;
-  HIP_TRY(c, hipMemcpy2DAsync(s->pair + slot, 2 * sizeof(afs_frame), src, sizeof(afs_frame),
+  afs_frame *pair = s->pair.as<afs_frame>();
+  HIP_TRY(c, hipMemcpy2DAsync(pair + slot, 2 * sizeof(afs_frame), src, sizeof(afs_frame),
                               sizeof(afs_frame), B, k, c->stream));
   if (!s->latched) {  // Synthesizer.cpp:522-532
     s->latched = true;
@@ -1142,42 +1115,32 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   }
   if (!out) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize: out is NULL");
   if (n < 1) n = 1;  // Synthesizer.cpp:543-546
-  const size_t nout = (size_t)B * (size_t)n;
-  double *dout;
-  bool host_out;
+  const size_t out_bytes = (size_t)B * (size_t)n * sizeof(double);
+  Staged<double> dout, dtaps;
   afs_status st;
-  if ((st = device_out(c, out, nout, &dout, &host_out)) != AFS_OK) return st;
-  if (host_out) {  // (back through the session's pinned buffer)
-    if (nout > s->hout_cap) {
-      if (s->hout) (void)hipHostFree(s->hout);
-      s->hout = nullptr;
-      s->hout_cap = 0;
-      HIP_TRY(c, hipHostMalloc((void **)&s->hout, nout * sizeof(double), hipHostMallocDefault));
-      s->hout_cap = nout;
-    }
-  }
-  double *dtaps = nullptr;
-  bool host_taps = false;
-  const size_t taps_bytes = nout * (size_t)c->n_taps * sizeof(double);
-  if (taps_out && (st = device_or_stage(c, taps_out, taps_bytes, &c->stage_taps, &c->stage_taps_bytes, &dtaps,
-                                        &host_taps)) != AFS_OK)
-    return st;
+  if ((st = dout.stage(c, out, out_bytes, c->stage_out)) != AFS_OK) return st;
+  if (dout.host) HIP_TRY(c, s->hout.reserve(out_bytes));  // (back through the session's pinned buffer)
+  if ((st = dtaps.stage(c, taps_out, out_bytes * (size_t)c->n_taps, c->stage_taps)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  SynthCall call{s->pair, 2, B, 1, n, dout, n, s->ws, s->rng, s->tree_lanes, s->bp, B, s->lanes, nullptr,
-                 plain_order(c)};
-  call.taps = dtaps;
-  call.tstride = n;
+  SynthCall call;
+  call.frames = pair, call.fstride = 2, call.rows = B;
+  call.ntrans = 1, call.hop = n;
+  call.out = dout.dev, call.ostride = n;
+  call.taps.out = dtaps.dev, call.taps.stride = n;
+  call.ws = s->ws.data(), call.rng = s->rng.as<int32_t>(), call.lanes = s->tree_lanes.data();
+  call.bp = s->bp, call.B = B, call.width = s->lanes;
+  call.so = plain_order(c);
   if ((st = run_call(c, call)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   // prevTube = *newTube (Synthesizer.cpp:633-637)
-  HIP_TRY(c, hipMemcpy2DAsync(s->pair, 2 * sizeof(afs_frame), s->pair + 1, 2 * sizeof(afs_frame),
+  HIP_TRY(c, hipMemcpy2DAsync(pair, 2 * sizeof(afs_frame), pair + 1, 2 * sizeof(afs_frame),
                               sizeof(afs_frame), B, hipMemcpyDeviceToDevice, c->stream));
   bool nf_sync = false;
-  if ((st = nonfinite_report(c, s->ws, s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(s->hout, dout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (host_taps) HIP_TRY(c, hipMemcpyAsync(taps_out, dtaps, taps_bytes, hipMemcpyDeviceToHost, c->stream));
+  if ((st = nonfinite_report(c, s->ws.data(), s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
+  if ((st = dout.copy_back(c, s->hout.data())) != AFS_OK) return st;
+  if ((st = dtaps.copy_back(c)) != AFS_OK) return st;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a session call always waits: its audio is due now)
-  if (host_out) std::memcpy(out, s->hout, nout * sizeof(double));
+  if (dout.host) std::memcpy(out, s->hout.data(), out_bytes);
   if (produced) *produced = n;
   return fill_report(c, rep, (int64_t)B * n);
 }
@@ -1202,32 +1165,23 @@ afs_status afs_session_rng_draws(afs_session *s, int64_t *draws) {
   if (!s || !draws) return AFS_ERR_INVALID_ARGUMENT;
   afs_ctx *c = s->ctx;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  return draws_of(c, s->ws, s->B, draws);
+  return draws_of(c, s->ws.data(), s->B, draws);
 }
 
 afs_status afs_af_to_frames(afs_ctx *c, const double *params, int64_t n, afs_frame *frames) {
   if (!c) return AFS_ERR_INVALID_ARGUMENT;
   if (!params || !frames || n <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_af_to_frames: bad args");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  const double *dp = params;
-  void *tmp_p = nullptr, *tmp_f = nullptr;
-  const bool host_p = !is_device_ptr(params), host_f = !is_device_ptr(frames);
-  afs_frame *df = frames;
-  if (host_p) {
-    HIP_TRY(c, hipMalloc(&tmp_p, (size_t)n * 16 * sizeof(double)));
-    HIP_TRY(c, hipMemcpyAsync(tmp_p, params, (size_t)n * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    dp = (const double *)tmp_p;
-  }
-  if (host_f) {
-    HIP_TRY(c, hipMalloc(&tmp_f, (size_t)n * sizeof(afs_frame)));
-    HIP_TRY(c, hipMemcpyAsync(tmp_f, frames, (size_t)n * sizeof(afs_frame), hipMemcpyHostToDevice, c->stream));
-    df = (afs_frame *)tmp_f;
-  }
-  HIP_TRY(c, afs::launch_af_to_frames(dp, n, df, c->stream));
-  if (host_f) HIP_TRY(c, hipMemcpyAsync(frames, df, (size_t)n * sizeof(afs_frame), hipMemcpyDeviceToHost, c->stream));
+  afs::DeviceBuf tmp_p, tmp_f;  // (freed on every return path)
+  Staged<const double> dp;
+  Staged<afs_frame> df;
+  afs_status s;
+  if ((s = dp.stage(c, params, (size_t)n * 16 * sizeof(double), tmp_p, true)) != AFS_OK) return s;
+  // (uploaded first: what the kernel leaves alone of a frame stays the caller's)
+  if ((s = df.stage(c, frames, (size_t)n * sizeof(afs_frame), tmp_f, true)) != AFS_OK) return s;
+  HIP_TRY(c, afs::launch_af_to_frames(dp.dev, n, df.dev, c->stream));
+  if ((s = df.copy_back(c)) != AFS_OK) return s;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (tmp_p) (void)hipFree(tmp_p);
-  if (tmp_f) (void)hipFree(tmp_f);
   return AFS_OK;
 }
 
@@ -1236,28 +1190,15 @@ afs_status afs_to_int16(afs_ctx *c, const double *samples, int64_t n, int16_t *o
   if (n == 0) return AFS_OK;  // empty views may carry null pointers
   if (!samples || !out || n < 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_to_int16: bad args");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  const bool host_in = !is_device_ptr(samples), host_out = !is_device_ptr(out);
-  struct Staging {  // freed on every return path
-    void *in = nullptr, *out = nullptr;
-    ~Staging() {
-      if (in) (void)hipFree(in);
-      if (out) (void)hipFree(out);
-    }
-  } tmp;
-  const double *din = samples;
-  int16_t *dout = out;
-  if (host_in) {
-    HIP_TRY(c, hipMalloc(&tmp.in, (size_t)n * sizeof(double)));
-    HIP_TRY(c, hipMemcpyAsync(tmp.in, samples, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    din = (const double *)tmp.in;
-  }
-  if (host_out) {
-    HIP_TRY(c, hipMalloc(&tmp.out, (size_t)n * sizeof(int16_t)));
-    dout = (int16_t *)tmp.out;
-  }
-  HIP_TRY(c, afs::launch_to_int16(din, dout, n, c->stream));
-  if (host_out) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-  if (host_in || host_out || !(c->cfg.flags & AFS_ASYNC)) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  afs::DeviceBuf tmp_in, tmp_out;  // (freed on every return path)
+  Staged<const double> din;
+  Staged<int16_t> dout;
+  afs_status s;
+  if ((s = din.stage(c, samples, (size_t)n * sizeof(double), tmp_in, true)) != AFS_OK) return s;
+  if ((s = dout.stage(c, out, (size_t)n * sizeof(int16_t), tmp_out)) != AFS_OK) return s;
+  HIP_TRY(c, afs::launch_to_int16(din.dev, dout.dev, n, c->stream));
+  if ((s = dout.copy_back(c)) != AFS_OK) return s;
+  if (din.host || dout.host || !(c->cfg.flags & AFS_ASYNC)) HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
 
@@ -1356,38 +1297,37 @@ afs_status afs_play_target_sequences(afs_ctx *c, const double *shapes, int32_t n
   }
   const size_t seq_bytes = seq.size() * sizeof(double);
   const size_t row_bytes = (size_t)B * sizeof(int32_t), ord_bytes = order.size() * sizeof(int32_t);
-  if ((s = ensure(c, &c->tgt, &c->tgt_bytes, seq_bytes + row_bytes + ord_bytes)) != AFS_OK) return s;
-  double *dseq = (double *)c->tgt;
-  int32_t *drow = (int32_t *)((char *)c->tgt + seq_bytes);
-  int32_t *dord = order.empty() ? nullptr : (int32_t *)((char *)c->tgt + seq_bytes + row_bytes);
+  HIP_TRY(c, c->tgt.reserve(seq_bytes + row_bytes + ord_bytes));
+  double *dseq = c->tgt.as<double>();
+  int32_t *drow = (int32_t *)(c->tgt.as<char>() + seq_bytes);
+  int32_t *dord = order.empty() ? nullptr : (int32_t *)(c->tgt.as<char>() + seq_bytes + row_bytes);
   HIP_TRY(c, hipMemcpyAsync(dseq, seq.data(), seq_bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(drow, row.data(), row_bytes, hipMemcpyHostToDevice, c->stream));
   if (dord) HIP_TRY(c, hipMemcpyAsync(dord, order.data(), ord_bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors die with this call
-  const uint32_t *dseeds;
-  double *dout;
-  bool host_out;
+  Seeds dseeds;
+  Staged<double> dout;
   if ((s = seeds_to_device(c, seeds, B, &dseeds)) != AFS_OK) return s;
-  if ((s = device_out(c, out, (size_t)B * T, &dout, &host_out)) != AFS_OK) return s;
-  if ((s = fresh_state(c, B, width, dseeds)) != AFS_OK) return s;
+  if ((s = dout.stage(c, out, (size_t)B * (size_t)T * sizeof(double), c->stage_out)) != AFS_OK) return s;
+  if ((s = fresh_state(c, B, width, dseeds.dev)) != AFS_OK) return s;
   // time chunks of Tc samples: Tc + 1 frames per sequence (the first repeats the previous
   // chunk's last), at most 1 GiB of frames
   const int64_t budget = (int64_t)1 << 30;
   const int64_t Tc = std::max<int64_t>(1, std::min<int64_t>({T, 65536, budget / ((int64_t)Q * (int64_t)sizeof(afs_frame)) - 1}));
-  if ((s = ensure(c, &c->stage_in, &c->stage_in_bytes, (size_t)Q * (size_t)(Tc + 1) * sizeof(afs_frame))) != AFS_OK)
-    return s;
-  afs_frame *dframes = (afs_frame *)c->stage_in;
+  HIP_TRY(c, c->stage_in.reserve((size_t)Q * (size_t)(Tc + 1) * sizeof(afs_frame)));
+  afs_frame *dframes = c->stage_in.as<afs_frame>();
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   for (int64_t k0 = 0; k0 < T; k0 += Tc) {
     const int nk = (int)std::min<int64_t>(Tc, T - k0);
     HIP_TRY(c, afs::launch_target_frames(dseq, Q, plan, k0, nk + 1, Tc + 1, dframes, c->stream));
-    SynthCall call{dframes, Tc + 1, Q, nk, 1, dout + k0, T, c->ws, c->rng, c->tree_lanes, pad64(B), B, width, drow,
-                   plain_order(c)};
+    SynthCall call = context_call(c, B, width);
+    call.frames = dframes, call.fstride = Tc + 1, call.rows = Q, call.frame_row = drow;
+    call.ntrans = nk, call.hop = 1;
+    call.out = dout.dev + k0, call.ostride = T;
     call.so.order = dord;
     if ((s = run_call(c, call)) != AFS_OK) return s;
   }
-  return finish_call(c, B, (int64_t)B * T, (int64_t)B * T, out, dout, host_out, nonfinite, rep,
-                     (c->cfg.flags & AFS_ASYNC) != 0);
+  return finish_call(c, B, (int64_t)B * T, dout, Staged<double>{}, nonfinite, rep, (c->cfg.flags & AFS_ASYNC) != 0);
 }
 
 }  // extern "C"

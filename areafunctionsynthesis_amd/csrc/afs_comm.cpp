@@ -369,14 +369,14 @@ afs_status afs_multi_synthesize(afs_ctx *const *ctxs, afs_comm *const *comms, in
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     if (b == 0) continue;
-    if ((s = afs::ensure(c, &c->m_out, &c->m_out_bytes, (size_t)(b * T) * sizeof(double))) != AFS_OK) return s;
-    if ((s = afs::ensure(c, &c->m_pcm, &c->m_pcm_bytes, (size_t)(b * T) * sizeof(int16_t))) != AFS_OK) return s;
-    if ((s = afs::ensure(c, &c->m_nf, &c->m_nf_bytes, (size_t)b)) != AFS_OK) return s;
+    HIP_TRY(c, c->m_out.reserve((size_t)(b * T) * sizeof(double)));
+    HIP_TRY(c, c->m_pcm.reserve((size_t)(b * T) * sizeof(int16_t)));
+    HIP_TRY(c, c->m_nf.reserve((size_t)b));
     // (queued on this device's stream; the host moves on to the next device)
     if ((s = afs::synthesize_async(c, frames + first[(size_t)i] * F, seeds + first[(size_t)i], (int32_t)b, F, hop,
-                                   (double *)c->m_out, (uint8_t *)c->m_nf, lanes)) != AFS_OK)
+                                   c->m_out.as<double>(), c->m_nf.as<uint8_t>(), lanes)) != AFS_OK)
       return s;
-    HIP_TRY(c, afs::launch_to_int16((const double *)c->m_out, (int16_t *)c->m_pcm, b * T, c->stream));
+    HIP_TRY(c, afs::launch_to_int16(c->m_out.as<double>(), c->m_pcm.as<int16_t>(), b * T, c->stream));
   }
   for (int i = 0; i < n; ++i) HIP_TRY(ctxs[i], hipEventRecord(ctxs[i]->ev1, ctxs[i]->stream));
   int16_t *root = pcm_out;
@@ -387,9 +387,8 @@ afs_status afs_multi_synthesize(afs_ctx *const *ctxs, afs_comm *const *comms, in
                      "ctxs[0]'s device %d", out_dev, c0->cfg.device);
   if (host_out) {
     HIP_TRY(c0, hipSetDevice(c0->cfg.device));
-    if ((s = afs::ensure(c0, &c0->m_root, &c0->m_root_bytes, (size_t)B * (size_t)T * sizeof(int16_t))) != AFS_OK)
-      return s;
-    root = (int16_t *)c0->m_root;
+    HIP_TRY(c0, c0->m_root.reserve((size_t)B * (size_t)T * sizeof(int16_t)));
+    root = c0->m_root.as<int16_t>();
   }
   std::vector<int64_t> counts((size_t)n);
   for (int i = 0; i < n; ++i) counts[(size_t)i] = cnt[(size_t)i] * T;
@@ -402,7 +401,7 @@ afs_status afs_multi_synthesize(afs_ctx *const *ctxs, afs_comm *const *comms, in
   if (rccl().GroupStart() != ncclSuccess) return afs::fail(c0, AFS_ERR_HIP, "ncclGroupStart failed");
   afs_status gs = AFS_OK;
   for (int i = 0; i < n && gs == AFS_OK; ++i)
-    gs = gather_post(comms[i], (const int16_t *)ctxs[i]->m_pcm, counts[(size_t)i], i == 0 ? root : nullptr,
+    gs = gather_post(comms[i], ctxs[i]->m_pcm.as<int16_t>(), counts[(size_t)i], i == 0 ? root : nullptr,
                      i == 0 ? rb0 : std::vector<size_t>());
   const ncclResult_t ge = rccl().GroupEnd();
   if (gs != AFS_OK || ge != ncclSuccess) {
@@ -429,7 +428,7 @@ afs_status afs_multi_synthesize(afs_ctx *const *ctxs, afs_comm *const *comms, in
     afs_ctx *c = ctxs[i];
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (cnt[(size_t)i] > 0)
-      HIP_TRY(c, hipMemcpyAsync(nonfinite + first[(size_t)i], c->m_nf, (size_t)cnt[(size_t)i], hipMemcpyDeviceToHost,
+      HIP_TRY(c, hipMemcpyAsync(nonfinite + first[(size_t)i], c->m_nf.data(), (size_t)cnt[(size_t)i], hipMemcpyDeviceToHost,
                                 c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if ((s = afs_comm_synchronize(comms[i])) != AFS_OK) return s;

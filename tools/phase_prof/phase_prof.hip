@@ -101,16 +101,30 @@ extern "C" int pp_run(const afs_frame *frames, const uint32_t *seeds, int B, int
   int32_t *dorder = nullptr;
   const int64_t hstride = plan_hop_slots(0, T, hop);
   CK(hipMalloc(&dplan, (size_t)B * (g_hops ? hstride * hop : T) * PLAN_RECORD_BYTES));
-  TreeArgs a{dt, df, F, nullptr, hop, 0, T, dout, T, dplan, T, dlanes, dlds, B, ht->uni, nullptr, 0, dp25, T};
+  TreeArgs a{};
+  a.tab = dt, a.uni = ht->uni;
+  a.frames = df, a.frame_stride = F;
+  a.hop = hop, a.s_begin = 0, a.s_end = T;
+  a.out = dout, a.out_stride = T;
+  a.plan = dplan, a.plan_stride = T;
+  a.lane_state = dlanes, a.lds_state = dlds, a.B = B;
+  a.p25 = dp25, a.p25_stride = T;
+  PlanArgs pa{};
+  pa.tab = dt, pa.uo = &dt->consts.sec[0];
+  pa.frames = df, pa.frame_stride = F;
+  pa.rows = B, pa.hop = hop;
+  pa.s_begin = 0, pa.s_end = T;
+  pa.plan = dplan, pa.plan_stride = T;
   if (!g_hops) {
-    PlanArgs pa{dt, df, F, B, hop, 0, T, dplan, T, 0, &dt->consts.sec[0]};
     CK(launch_plan(pa, nullptr));
   } else {
     // hop records, every mixed hop a compact slot; the slots ordered by noise class as the library's
     // slot order keys them (afs_capi.cpp shape_order), so that a wave's utterances share a variant
     CK(hipMalloc(&dhops, sizeof(PlanHop) * (size_t)B * hstride));
     CK(hipMalloc(&dwork, (size_t)plan_work_bytes(B, hstride)));
-    PlanArgs pa{dt, df, F, B, hop, 0, T, dplan, 0, 0, &dt->consts.sec[0], dhops, hstride, dwork, true, (int64_t)B * hstride};
+    pa.plan_stride = 0;
+    pa.hops = dhops, pa.hop_stride = hstride;
+    pa.work = dwork, pa.compact = true, pa.dense_cap = (int64_t)B * hstride;
     CK(launch_plan_hops(pa, nullptr));
     std::vector<PlanHop> hh((size_t)B * hstride);
     CK(hipMemcpy(hh.data(), dhops, sizeof(PlanHop) * hh.size(), hipMemcpyDeviceToHost));
