@@ -32,25 +32,25 @@ __global__ void __launch_bounds__(64 * Geom<W>::WPB, AFS_TREE_MIN_WAVES) tree_sy
 // workgroup, two per SIMD
 template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(256, 2) tree_pair_kernel(TreeArgs a) {
-  __shared__ WaveLdsT<TW> lds;
+  __shared__ PairLdsT<TW> lds;
   __shared__ int pattern[5];
   tree_pair_body<MODEL, HOPS, false, TAPS>(a, lds, pattern);
 }
 // the voice kernel's pairs: two waves per utterance, each may take a whole SIMD's registers
 template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(128, 2) tree_pair64_kernel(TreeArgs a) {
-  __shared__ WaveLdsT<64> lds;
+  __shared__ PairLdsT<64> lds;
   tree_pair64_body<MODEL, HOPS, false, TAPS>(a, lds);
 }
 template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(256, 2) tree_pair_ragged_kernel(TreeArgs a) {
-  __shared__ WaveLdsT<TW> lds;
+  __shared__ PairLdsT<TW> lds;
   __shared__ int pattern[5];
   tree_pair_body<MODEL, HOPS, false, TAPS, true>(a, lds, pattern);
 }
 template <int MODEL, bool HOPS, bool TAPS = false>
 __global__ void __launch_bounds__(128, 2) tree_pair64_ragged_kernel(TreeArgs a) {
-  __shared__ WaveLdsT<64> lds;
+  __shared__ PairLdsT<64> lds;
   tree_pair64_body<MODEL, HOPS, false, TAPS, true>(a, lds);
 }
 #endif

@@ -2418,12 +2418,17 @@ AFS_HD inline void sample_step(Xc &x, double *X, const Uni &U, const Consts &C, 
 // everything one wave writes and the other reads (the dynamic slots' L, R, E, D and the static
 // slots' D, the dipole samples, the rows, the solution, the published pressures and flows).
 //   P1  DYN: interpolation, the glottis, the dynamic slots' network
-//       STAT: the static slots' D, the glottis and its commit, targets, noise
+//       STAT: the static slots' D, the glottis and its commit, targets, noise -- hop mode: on the
+//       plan words DYN left in LDS in the previous sample's P3 (one LDS read at the top of the sample;
+//       STAT holds no hop record and evaluates no word)
 //       (no barrier inside P1: both waves evaluate the glottis, STAT commits it.  The glottis once,
 //       on DYN, with a fifth barrier measured -2.7 %; STAT evaluating only the upper area -1 %)
 //   P2  rows of each role's slots
 //   P3  STAT: the arm solver, in the lean form (the full form spills: -17 %)
-//       DYN: the rand() blocks ahead, beside the solver (on STAT after it: -4.5 %)
+//       DYN: the rand() blocks ahead, beside the solver (on STAT after it: -4.5 %), then feed(): hop
+//       mode's plan words of the next sample from the hop record DYN holds, stored to LDS in front of
+//       P3's barrier (tree_kernel.h tree_pair_run: STAT's spills in the time loop 27 loads + 14 stores
+//       -> 8 + 0 in its heaviest noise variant, none in the others; +2.3 %, profiles/AB_LOG.md)
 //   P4  the state update of each role's slots; DYN: the radiated flow (R.sample)
 // (the measurements: profiles/AB_LOG.md, round 6, raw runs in profiles/r06_pair_ab.txt)
 // Both waves read the glottis displacements at the start of P1 and STAT commits the new ones in P1:
@@ -2454,9 +2459,12 @@ AFS_HD inline void rng_ring_pos_store(Xc &x, double *X) {
     }
   });
 }
-template <int W, int MODEL, int NZ, int ROLE, bool VARLOSS, bool TAPS = false, class Xc>
+struct NoPlanFeed {  // (the host emulators: their caller sets every sample's plan words itself)
+  AFS_HD void operator()() const {}
+};
+template <int W, int MODEL, int NZ, int ROLE, bool VARLOSS, bool TAPS = false, class Xc, class Feed = NoPlanFeed>
 AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par,
-                                      const TapSet *taps = nullptr) {
+                                      const TapSet *taps = nullptr, Feed feed = Feed{}) {
   static_assert(ROLE == ROLE_DYN || ROLE == ROLE_STAT, "a wave pair's roles");
   constexpr bool STAT = ROLE == ROLE_STAT;
   AFS_SCHED_BARRIER();
@@ -2517,6 +2525,7 @@ AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Cons
     rng_ring_pos_load<W>(x, X);
     rng_ahead<W>(x, X);
     rng_ring_pos_store<W>(x, X);
+    feed();  // (the next sample's plan words for STAT, tree_kernel.h tree_pair_run)
     x.mark(PH_RNGP);
   }
   x.bar();
@@ -2535,13 +2544,13 @@ AFS_HD inline void sample_step_pair_v(Xc &x, double *X, const Uni &U, const Cons
   x.bar();
   x.mark(PH_P4WAIT);
 }
-template <int W, int MODEL, int NZ, int ROLE, bool TAPS = false, class Xc>
+template <int W, int MODEL, int NZ, int ROLE, bool TAPS = false, class Xc, class Feed = NoPlanFeed>
 AFS_HD inline void sample_step_pair(Xc &x, double *X, const Uni &U, const Consts &C, double ratio, int par,
-                                    const TapSet *taps = nullptr) {
+                                    const TapSet *taps = nullptr, Feed feed = Feed{}) {
   if (U.opt.glottis_loss == AFS_ENTRANCE_LOSS_VARIABLE)
-    sample_step_pair_v<W, MODEL, NZ, ROLE, true, TAPS>(x, X, U, C, ratio, par, taps);
+    sample_step_pair_v<W, MODEL, NZ, ROLE, true, TAPS>(x, X, U, C, ratio, par, taps, feed);
   else
-    sample_step_pair_v<W, MODEL, NZ, ROLE, false, TAPS>(x, X, U, C, ratio, par, taps);
+    sample_step_pair_v<W, MODEL, NZ, ROLE, false, TAPS>(x, X, U, C, ratio, par, taps, feed);
 }
 
 }  // namespace tree

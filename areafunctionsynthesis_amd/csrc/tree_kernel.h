@@ -215,6 +215,13 @@ struct WaveLdsT {
   double X[Geom<W>::UPB][X_STRIDE];
 };
 using WaveLds = WaveLdsT<TW>;
+// ... and of a wave-pair block: beside them, the plan words the DYN wave hands the STAT wave, one
+// record of the coming sample per utterance (tree_pair_run).  Outside X: the saved image, X_STRIDE
+// and the taps' slots stay what they are.
+template <int W>
+struct PairLdsT : WaveLdsT<W> {
+  uint64_t planw[Geom<W>::UPB][PLAN_WORDS];
+};
 
 // Whether this block has anything to do: not a launch of the hop-mode fast path whose mixed hops
 // overflowed K5's compact slots (the host runs the call through the chunked path instead,
@@ -506,7 +513,7 @@ __device__ __forceinline__ void tree_synth_body(const TreeArgs &a, WaveLdsT<W> &
 // ---------------------------------------------------------------------------
 // (W = 64: the voice kernel's pairs, one utterance per workgroup of two waves, tree_pair64_body)
 template <int MODEL, bool HOPS, int NZ, int ROLE, bool PROF = false, int W = TW, bool TAPS = false, bool RAGGED = false>
-__device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &lds, int grp, uint64_t *prof = nullptr) {
+__device__ __forceinline__ void tree_pair_run(const TreeArgs &a, PairLdsT<W> &lds, int grp, uint64_t *prof = nullptr) {
   constexpr int UPB_ = Geom<W>::UPB;
   constexpr int NT = 2 * 64 * Geom<W>::WPB;  // threads per workgroup (a pair per wave of the one-wave kernel)
   using S = Shape<W>;
@@ -540,20 +547,32 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
   const int64_t n = block_s_end<RAGGED>(a) - a.s_begin;  // (ragged calls: the block's utterances may end before s_end)
   int k = (int)(a.s_begin / hop) + 1, i = (int)(a.s_begin % hop);
   if constexpr (ROLE == ROLE_DYN) frame_load<W>(gl, R, X, fu + (k - 1), fu + k);
+  // Hop mode: the DYN wave owns the hop-record feed.  The record's word gl % 16 (its kind and inputs,
+  // whether the hop is mixed, its dense records) lives in DYN's registers; in P3 of sample t, beside
+  // the STAT wave's solver, DYN evaluates the word of sample t + 1 -- a function of the record and of
+  // that sample's ratio alone -- and stores it to lds.planw[g]; the STAT wave, which has no registers
+  // to spare, only reads its word at the top of the sample.  No barrier of its own: the store is in
+  // front of P3's barrier of sample t and the read behind its P4's (the launch's first word: in front
+  // of and behind the __syncthreads below), and DYN's next store, in P3 of sample t + 1, is behind that
+  // sample's P1 and P2 barriers, which STAT reaches with its read complete.
+  // (Dense records without hops, hop 1: the STAT wave keeps its read of pl[] a sample ahead -- a
+  // pointer and a word, nothing to evaluate; on DYN it would sit beside that form's NextFrame.)
+  constexpr bool FEED = HOPS && ROLE == ROLE_DYN;
+  const int pw = gl & (PLAN_WORDS - 1);
   const PlanHop *hr = HOPS ? a.hops + row * a.hop_stride : nullptr;
   double hp[4] = {0.0, 0.0, 0.0, 0.0};
   uint32_t hkind = PK_CONST;
   bool hmixed = !HOPS;
   const uint64_t *pd = nullptr;
   auto hop_load = [&](const PlanHop *h) {
-    const double2 *q = reinterpret_cast<const double2 *>(h->p[gl & (PLAN_WORDS - 1)]);
+    const double2 *q = reinterpret_cast<const double2 *>(h->p[pw]);
     const double2 v0 = q[0], v1 = q[1];
     hp[0] = v0.x; hp[1] = v0.y; hp[2] = v1.x; hp[3] = v1.y;
-    hkind = h->kind[gl & (PLAN_WORDS - 1)];
+    hkind = h->kind[pw];
     hmixed = h->mixed != 0;
-    pd = a.plan + (int64_t)h->dense * hop * PLAN_WORDS + (gl & (PLAN_WORDS - 1));
+    pd = a.plan + (int64_t)h->dense * hop * PLAN_WORDS + pw;
   };
-  if constexpr (HOPS && ROLE == ROLE_STAT) hop_load(hr);
+  if constexpr (FEED) hop_load(hr);
   NextFrame<W> nf{};
   const int o_line = (int)((reinterpret_cast<uintptr_t>(o) >> 3) & 15);
   double wo = 0.0, wp = 0.0;
@@ -568,9 +587,18 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
       hp[1] = R.rpend;
     }
   }
-  __syncthreads();  // (the LDS image and X_FRAME in place for both roles)
+  uint64_t *const planw = lds.planw[g];
+  // the word of sample t + 1 into planw (lanes of the same word store the same value)
+  auto plan_store = [&](uint64_t v) {
+    if (W == PLAN_WORDS || gl < PLAN_WORDS) planw[pw] = v;
+  };
+  if constexpr (FEED) {  // (the launch's first sample: its ratio as the step below takes it)
+    const uint64_t ev = plan_word_fast(hkind, hp, hop_ratio(i, dhop, inv_hop));
+    plan_store(hmixed ? pd[i * PLAN_WORDS] : ev);
+  }
+  __syncthreads();  // (the LDS image, X_FRAME and the first plan words in place for both roles)
   uint64_t next = 0;
-  if constexpr (ROLE == ROLE_STAT) next = hmixed ? (HOPS ? pd[i * PLAN_WORDS] : pl[0]) : 0;
+  if constexpr (!HOPS && ROLE == ROLE_STAT) next = pl[0];
   if constexpr (ROLE == ROLE_STAT) {
     if (ex.prio == 3) AFS_SETPRIO(2);  // (the whole launch; modes 1, 2: sample_step_pair)
   }
@@ -581,17 +609,32 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
     const int64_t tn = t + 1 < n ? t + 1 : t;
     if constexpr (ROLE == ROLE_STAT) {
       if constexpr (HOPS) {
-        const uint64_t ev = plan_word_fast(hkind, hp, ratio);
-        R.planw = hmixed ? next : ev;
-        next = *(hmixed ? pd + (i + 1 < hop ? i + 1 : i) * PLAN_WORDS : reinterpret_cast<const uint64_t *>(hr));
+        R.planw = planw[pw];  // (what DYN stored in the previous sample's P3, or before the loop)
       } else {
         R.planw = next;
         next = pl[tn * PLAN_WORDS];
       }
     } else if constexpr (!HOPS) {
       if (i + 1 == hop && t + 1 < n) nf.load(gl, fu + k + 1);
+    } else {
+      // The loads for the next sample's word, a phase group and more ahead of their use in P3: inside
+      // a hop the next dense word (a hop that is not mixed reads its own record's first word: a
+      // cache hit, no branch), on a hop's last sample the next hop's record -- one sample earlier
+      // than a wave that evaluated at the top of the sample would need it, as NextFrame's fields.
+      if (i + 1 < hop) next = *(hmixed ? pd + (i + 1) * PLAN_WORDS : reinterpret_cast<const uint64_t *>(hr));
+      else if (t + 1 < n) hop_load(++hr);
     }
-    sample_step_pair<W, MODEL, NZ, ROLE, TAPS>(ex, X, a.uni, C, ratio, (int)(t & 1), &a.taps);
+    // (FEED, in P3 behind the rand() blocks: sample t + 1's word from the ratio its own step will take,
+    // hop_ratio of the same arguments; behind the launch's or the block's last sample nothing reads it)
+    auto feed = [&]() {
+      if constexpr (FEED) {
+        const bool last = i + 1 == hop;
+        const uint64_t ev = plan_word_fast(hkind, hp, hop_ratio(last ? 0 : i + 1, dhop, inv_hop));
+        if (last && t + 1 < n && hmixed) next = pd[0];
+        plan_store(hmixed ? next : ev);
+      }
+    };
+    sample_step_pair<W, MODEL, NZ, ROLE, TAPS>(ex, X, a.uni, C, ratio, (int)(t & 1), &a.taps, feed);
     if constexpr (TAPS && ROLE == ROLE_DYN) tw.collect(a, X, gl, valid, t, n);
     if constexpr (ROLE == ROLE_DYN) {
       const int j = (o_line + (int)t) & 15;
@@ -616,9 +659,6 @@ __device__ __forceinline__ void tree_pair_run(const TreeArgs &a, WaveLdsT<W> &ld
           } else {
             frame_shift<W>(gl, R, X, nf);
           }
-        } else if constexpr (HOPS) {
-          hop_load(++hr);
-          if (hmixed) next = pd[0];
         }
       }
       ex.bar();
@@ -679,7 +719,7 @@ __device__ unsigned int pair_cu_slots[2048];
 // wave index.  Any placement gives a valid pairing; this only balances the SIMDs (against roles by
 // the wave index, the wave slot's or the block's parity: profiles/r06_pair_ab.txt).
 template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false, bool RAGGED = false>
-__device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &lds, int *pattern,
+__device__ __forceinline__ void tree_pair_body(const TreeArgs &a, PairLdsT<TW> &lds, int *pattern,
                                                uint64_t *prof = nullptr) {
   if (!block_has_work<TW, RAGGED>(a)) return;
   const int wave = (int)threadIdx.x / 64;
@@ -731,7 +771,7 @@ __device__ __forceinline__ void tree_pair_body(const TreeArgs &a, WaveLdsT<TW> &
 // DYN and wave 1 STAT, for batches that leave a SIMD to each wave (afs_tree.h TREE_PAIR64_MAX): the
 // sample's chain split over two SIMDs instead of one wave's.
 template <int MODEL, bool HOPS, bool PROF = false, bool TAPS = false, bool RAGGED = false>
-__device__ __forceinline__ void tree_pair64_body(const TreeArgs &a, WaveLdsT<64> &lds, uint64_t *prof = nullptr) {
+__device__ __forceinline__ void tree_pair64_body(const TreeArgs &a, PairLdsT<64> &lds, uint64_t *prof = nullptr) {
   if (!block_has_work<64, RAGGED>(a)) return;
   const bool stat = threadIdx.x >= 64;
   if (!stat) {

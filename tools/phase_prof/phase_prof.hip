@@ -23,7 +23,7 @@ constexpr int PW = PP_W;
 constexpr int PWPB = 4, PUPB = Geom<PW>::UPB;
 template <bool HOPS>
 __global__ void __launch_bounds__(256, 2) tree_prof_kernel(TreeArgs a, uint64_t *prof) {
-  __shared__ WaveLdsT<TW> lds;
+  __shared__ PairLdsT<TW> lds;
   __shared__ int pattern[5];
   tree_pair_body<AFS_GLOTTIS_TRIANGULAR, HOPS, true>(a, lds, pattern, prof);
 }
@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256, 2) tree_prof_kernel(TreeArgs a, uint64_t 
 constexpr int PWPB = 2, PUPB = 1;
 template <bool HOPS>
 __global__ void __launch_bounds__(128, 2) tree_prof_kernel(TreeArgs a, uint64_t *prof) {
-  __shared__ WaveLdsT<64> lds;
+  __shared__ PairLdsT<64> lds;
   tree_pair64_body<AFS_GLOTTIS_TRIANGULAR, HOPS, true>(a, lds, prof);
 }
 #else
