@@ -200,27 +200,34 @@ hipError_t launch_tree_reset(void *lane_state, double *lds_state, int B, const u
   return hipGetLastError();
 }
 
-// One launch per (glottis model, plan mode): K<MODEL, HOPS>() names the kernel.
-template <class K>
-static void launch_model_hops(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st, K kernel) {
-  const bool two = a.uni.opt.glottis_model == AFS_GLOTTIS_TWO_MASS;
-  if (a.hops) {
-    if (two) hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TWO_MASS>{}, std::true_type{}), grid, block, 0, st, a);
-    else hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TRIANGULAR>{}, std::true_type{}), grid, block, 0, st, a);
-  } else {
-    if (two) hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TWO_MASS>{}, std::false_type{}), grid, block, 0, st, a);
-    else hipLaunchKernelGGL(kernel(std::integral_constant<int, AFS_GLOTTIS_TRIANGULAR>{}, std::false_type{}), grid, block, 0, st, a);
-  }
+// Run-time switches as template arguments: f(std::bool_constant<B>{}...) for the bools' values.
+// (The order of the bools is the order the kernels are instantiated in, true first, the first bool
+// outermost, and so their order in the code object: the callers keep the order the kernels always
+// had, which keeps every kernel's pc-relative addresses, tools/kernel_meta.py --text.)
+template <class F>
+static void with_bools(F f) { f(); }
+template <class F, class... Bs>
+static void with_bools(F f, bool b, Bs... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-// the one-wave kernel (every phase on one wave)
-template <int W, bool TAPS, bool RAGGED>
-static void launch_one_wave(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st) {
-  launch_model_hops(a, grid, block, st, [](auto m, auto h) {
-    if constexpr (RAGGED) return tree_synth_ragged_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>;
-    else return tree_synth_kernel<decltype(m)::value, decltype(h)::value, W, TAPS>;
-  });
+// One launch per (glottis model, plan mode): kernel(model, hops) names the kernel.
+template <class K>
+static void launch_model_hops(const TreeArgs &a, dim3 grid, dim3 block, hipStream_t st, K kernel) {
+  with_bools([&](auto hops, auto two) {
+    constexpr int MODEL = decltype(two)::value ? AFS_GLOTTIS_TWO_MASS : AFS_GLOTTIS_TRIANGULAR;
+    hipLaunchKernelGGL(kernel(std::integral_constant<int, MODEL>{}, hops), grid, block, 0, st, a);
+  }, a.hops != nullptr, a.uni.opt.glottis_model == AFS_GLOTTIS_TWO_MASS);
 }
+
+// kernel(model, hops) of a kernel family in launch_synth_w's form: NAME_ragged_kernel for a ragged
+// call, NAME_kernel otherwise, of (model, hops, the arguments that follow)
+#define AFS_TREE_KERNEL(NAME, ...)                                                                         \
+  [](auto m, auto h) {                                                                                     \
+    if constexpr (RAGGED) return NAME##_ragged_kernel<decltype(m)::value, decltype(h)::value, __VA_ARGS__>; \
+    else return NAME##_kernel<decltype(m)::value, decltype(h)::value, __VA_ARGS__>;                        \
+  }
 
 template <int W, bool TAPS, bool RAGGED>
 static void launch_synth_w(const TreeArgs &a, hipStream_t st) {
@@ -229,38 +236,25 @@ static void launch_synth_w(const TreeArgs &a, hipStream_t st) {
 #if AFS_PAIR
   if constexpr (W == TW) {  // (the one-wave kernel at 16 lanes is not instantiated in this build)
     static_assert(Geom<TW>::WPB == 2, "a wave pair per four utterances: 4 waves per 8-utterance block");
-    launch_model_hops(a, grid, dim3(256), st, [](auto m, auto h) {
-      if constexpr (RAGGED) return tree_pair_ragged_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
-      else return tree_pair_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
-    });
+    return launch_model_hops(a, grid, dim3(256), st, AFS_TREE_KERNEL(tree_pair, TAPS));
   } else if constexpr (W == 64) {
-    if (a.B <= TREE_PAIR64_MAX) {
-      launch_model_hops(a, grid, dim3(128), st, [](auto m, auto h) {
-        if constexpr (RAGGED) return tree_pair64_ragged_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
-        else return tree_pair64_kernel<decltype(m)::value, decltype(h)::value, TAPS>;
-      });
-      return;
-    }
+    if (a.B <= TREE_PAIR64_MAX) return launch_model_hops(a, grid, dim3(128), st, AFS_TREE_KERNEL(tree_pair64, TAPS));
   }
-  if constexpr (W != TW) launch_one_wave<W, TAPS, RAGGED>(a, grid, block, st);
-#else
-  launch_one_wave<W, TAPS, RAGGED>(a, grid, block, st);
 #endif
+  // the one-wave kernel (every phase on one wave)
+  if constexpr (!AFS_PAIR || W != TW) launch_model_hops(a, grid, block, st, AFS_TREE_KERNEL(tree_synth, W, TAPS));
 }
+#undef AFS_TREE_KERNEL
 
 hipError_t launch_tree_synth(const TreeArgs &a, int lanes, hipStream_t st) {
   if (a.B <= 0 || a.s_end <= a.s_begin) return hipSuccess;
   // (a ragged launch carries both arrays and a slot order with a block count: afs_ragged_order.h)
   const bool ragged = a.block_end || a.pad_standin;
   if (ragged && !(a.block_end && a.pad_standin && a.order && a.grid_blocks > 0)) return hipErrorInvalidValue;
-  if (a.taps.n > 0) {
-    if (a.taps.n > AFS_MAX_TAPS || !a.tap_out) return hipErrorInvalidValue;
-    if (lanes == 64) ragged ? launch_synth_w<64, true, true>(a, st) : launch_synth_w<64, true, false>(a, st);
-    else ragged ? launch_synth_w<TW, true, true>(a, st) : launch_synth_w<TW, true, false>(a, st);
-  } else {
-    if (lanes == 64) ragged ? launch_synth_w<64, false, true>(a, st) : launch_synth_w<64, false, false>(a, st);
-    else ragged ? launch_synth_w<TW, false, true>(a, st) : launch_synth_w<TW, false, false>(a, st);
-  }
+  if (a.taps.n > 0 && (a.taps.n > AFS_MAX_TAPS || !a.tap_out)) return hipErrorInvalidValue;
+  with_bools([&](auto taps, auto w64, auto rg) {
+    launch_synth_w<decltype(w64)::value ? 64 : TW, decltype(taps)::value, decltype(rg)::value>(a, st);
+  }, a.taps.n > 0, lanes == 64, ragged);
   return hipGetLastError();
 }
 
