@@ -43,6 +43,7 @@ EXPORTED = (
     "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times", "afs_multi_synthesize",
     "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps", "afs_section_currents",
     "afs_synthesize_ragged",
+    "afs_synthesize_pcm", "afs_synthesize_ragged_pcm", "afs_session_synthesize_pcm", "afs_memory_info_get",
 )
 
 
@@ -79,6 +80,10 @@ class AfsKernelTiming(ctypes.Structure):
     _fields_ = [("synth_ms", ctypes.c_double), ("synth_launches", ctypes.c_int32),
                 ("plan_ms", ctypes.c_double), ("plan_launches", ctypes.c_int32),
                 ("output_ms", ctypes.c_double), ("output_launches", ctypes.c_int32)]
+
+
+class AfsMemoryInfo(ctypes.Structure):
+    _fields_ = [("total_bytes", ctypes.c_int64), ("sample_buffer_bytes", ctypes.c_int64)]
 
 
 class AfsError(RuntimeError):
@@ -161,13 +166,21 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_section_currents.argtypes = [ctypes.c_int32, i32p, i32p]
     lib.afs_synthesize_ragged.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32, vp,
                                           ctypes.c_int64, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_synthesize_pcm.argtypes = [vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
+                                       vp, ctypes.POINTER(AfsReport)]
+    lib.afs_synthesize_ragged_pcm.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32, vp,
+                                              ctypes.c_int64, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_session_synthesize_pcm.argtypes = [vp, vp, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(AfsReport)]
+    lib.afs_memory_info_get.argtypes = [vp, ctypes.POINTER(AfsMemoryInfo)]
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",
                  "afs_to_int16", "afs_play_target_sequences", "afs_rng_draws", "afs_session_rng_draws", "afs_plan_hop_words",
                  "afs_kernel_times", "afs_kernel_times_ex", "afs_comm_unique_id", "afs_comm_create", "afs_comm_create_all",
                  "afs_gather_pcm", "afs_comm_fence", "afs_comm_synchronize", "afs_comm_gather_times",
                  "afs_multi_synthesize", "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps",
-                 "afs_section_currents", "afs_synthesize_ragged"):
+                 "afs_section_currents", "afs_synthesize_ragged", "afs_synthesize_pcm", "afs_synthesize_ragged_pcm",
+                 "afs_session_synthesize_pcm", "afs_memory_info_get"):
         getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -136,6 +136,10 @@ struct SynthCall {
   int rows = 0, ntrans = 0, hop = 0;
   double *out = nullptr;
   int64_t ostride = 0;
+  // the _pcm calls (out is null): the audio as int16 to pcm[u * pstride + s]; the flows of each launch
+  // pass through the context's flow window instead of `out`
+  int16_t *pcm = nullptr;
+  int64_t pstride = 0;
   void *ws = nullptr;
   int32_t *rng = nullptr;
   void *lanes = nullptr;
@@ -187,10 +191,20 @@ struct LaunchPlans {
 // so that every utterance's row sits at the same position in its 128-byte lines as its output row
 // (stride and base congruent to the output's modulo 16 doubles): K1 stores both through one
 // line-aligned window (tree_kernel.h).
+// A _pcm call keeps the flows in a window of the same shape (c->flow): rows of `per` rounded up to whole
+// lines, the base on a line, so every row of both windows starts a 128-byte line whatever the caller's
+// pcm looks like, and neither window grows with the call's length.
 afs_status p25_for(afs_ctx *c, const SynthCall &call, int64_t per, int64_t *stride) {
-  *stride = per + ((call.ostride - per) % 16 + 16) % 16;
+  const int64_t ostride = call.pcm ? (per + 15) / 16 * 16 : call.ostride;
+  *stride = per + ((ostride - per) % 16 + 16) % 16;
   HIP_TRY(c, c->p25.reserve(((size_t)call.B * (size_t)*stride + 32) * sizeof(double)));
+  if (call.pcm) HIP_TRY(c, c->flow.reserve(((size_t)call.B * (size_t)*stride + 16) * sizeof(double)));
   return AFS_OK;
+}
+// the flow window's first row: the first 128-byte line of c->flow
+double *flow_row0(const afs_ctx *c) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(c->flow.data());
+  return reinterpret_cast<double *>((p + 127) & ~(uintptr_t)127);
 }
 // the p25 base for the launch whose outputs start at `out`
 double *p25_row0(const afs_ctx *c, const double *out) {
@@ -212,16 +226,17 @@ afs::PlanArgs plan_args(const afs_ctx *c, const afs_frame *frames, int64_t fstri
   return pa;
 }
 
-// K1 over samples [s0, s1) of the call, then K6 over them (both timed).
+// K1 over samples [s0, s1) of the call, then K6 over them (both timed).  A _pcm call: K1's flows into
+// the flow window (rows of p25_stride, as p25's), K6's PCM form from there to the caller's pcm.
 afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, int64_t s1, const LaunchPlans &lp,
                                int64_t p25_stride) {
   const SlotOrder &so = call.so;
-  double *out = call.out + s0, *p25 = p25_row0(c, out);
+  double *out = call.pcm ? flow_row0(c) : call.out + s0, *p25 = p25_row0(c, out);
   afs::TreeArgs a{};
   a.tab = c->tab(), a.uni = c->host_tab.uni;
   a.frames = call.frames, a.frame_stride = call.fstride, a.frame_row = call.frame_row;
   a.hop = call.hop, a.s_begin = s0, a.s_end = s1;
-  a.out = out, a.out_stride = call.ostride;
+  a.out = out, a.out_stride = call.pcm ? p25_stride : call.ostride;
   a.plan = lp.plan, a.plan_stride = lp.plan_stride;
   a.hops = lp.hops, a.hop_stride = lp.hop_stride;
   a.skip_claims = lp.skip, a.skip_cap = lp.skip_cap;
@@ -245,9 +260,14 @@ afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, in
   hipEvent_t e2 = prof_event(c);
   prof_pair(c, e1, e2, 0);
   // K6: the glottal-tone filter and the output stage of the launch's samples
-  HIP_TRY(c, afs::launch_tree_output(c->tab(), (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
-                                     c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap,
-                                     call.ragged.row_hops, call.hop, s0));
+  if (call.pcm)
+    HIP_TRY(c, afs::launch_tree_output_pcm(c->tab(), (double *)call.ws, out, p25_stride, s1 - s0, call.B, p25,
+                                           c->cfg.options.radiation_from_skin, call.pcm + s0, call.pstride, c->stream,
+                                           lp.skip, lp.skip_cap, call.ragged.row_hops, call.hop, s0));
+  else
+    HIP_TRY(c, afs::launch_tree_output(c->tab(), (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
+                                       c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap,
+                                       call.ragged.row_hops, call.hop, s0));
   prof_pair(c, e2, prof_event(c), 2);
   return AFS_OK;
 }
@@ -517,8 +537,9 @@ afs_status fill_report(afs_ctx *c, afs_report *rep, int64_t samples) {
 // array, ev1, the non-finite flags and count, the copy of staged audio to a host `out`, then the wait
 // and the report.  The call returns without a wait only when it is asynchronous (`async`) and nothing
 // goes to host memory: no host `out` or taps, no report, no host flags.  `samples`: what the report
-// counts.
-afs_status finish_call(afs_ctx *c, int B, int64_t samples, const Staged<double> &out, const Staged<double> &taps,
+// counts.  (`out`: the audio as the call delivers it, doubles or the _pcm calls' int16.)
+template <class T>
+afs_status finish_call(afs_ctx *c, int B, int64_t samples, const Staged<T> &out, const Staged<double> &taps,
                        uint8_t *nonfinite, afs_report *rep, bool async) {
   afs_status s;
   if ((s = taps.copy_back(c)) != AFS_OK) return s;
@@ -749,6 +770,8 @@ struct Trajectories {
   double *out = nullptr;  // out[u * ostride + s]
   int64_t ostride = 0;
   double *taps_out = nullptr;  // the context's taps beside the audio, rows of ostride as well (null: none)
+  int16_t *pcm = nullptr;      // the _pcm calls, instead of out: pcm[u * pstride + s]
+  int64_t pstride = 0;
   int64_t samples = 0;         // what the report counts
   bool force_async = false;    // leave the stream running unless a host buffer needs a wait
   int lanes = 0;               // the tree kernel's lanes per utterance (0: chosen for B)
@@ -768,11 +791,16 @@ static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfini
   Frames fr;
   Seeds seeds;
   Staged<double> out, taps;
+  Staged<int16_t> pcm;
   if ((s = frames_to_device(c, t.frames, (size_t)B * (size_t)t.fstride, &fr)) != AFS_OK) return s;
   if ((s = seeds_to_device(c, t.seeds, B, &seeds)) != AFS_OK) return s;
   // (a ragged call's host out and taps go up first and come back whole: what lies past each row's
   // end is the caller's)
   if ((s = out.stage(c, t.out, out_bytes, c->stage_out, ragged)) != AFS_OK) return s;
+  // (a host pcm likewise when its rows have padding; it reaches to the end of the last row's samples)
+  const int64_t Tmax = (int64_t)(t.F - 1) * t.hop;
+  const size_t pcm_bytes = ((size_t)(B - 1) * (size_t)t.pstride + (size_t)Tmax) * sizeof(int16_t);
+  if ((s = pcm.stage(c, t.pcm, pcm_bytes, c->stage_pcm, ragged || t.pstride != Tmax)) != AFS_OK) return s;
   const int width = t.lanes > 0 ? t.lanes : lanes_for(c, B);
   if ((s = fresh_state(c, B, width, seeds.dev)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
@@ -781,12 +809,15 @@ static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfini
   call.frames = fr.dev, call.fstride = t.fstride, call.rows = B;
   call.ntrans = t.F - 1, call.hop = t.hop;
   call.out = out.dev, call.ostride = t.ostride;
+  call.pcm = pcm.dev, call.pstride = t.pstride;
   call.taps.out = taps.dev, call.taps.stride = t.ostride;
   s = ragged ? ragged_layout(c, t.num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, t.hop, &call)
              : shape_order(c, fr.dev, t.fstride, B, width, &call.so);
   if (s != AFS_OK) return s;
   if ((s = run_call(c, call)) != AFS_OK) return s;
-  return finish_call(c, B, t.samples, out, taps, nonfinite, rep, t.force_async || (c->cfg.flags & AFS_ASYNC));
+  const bool async = t.force_async || (c->cfg.flags & AFS_ASYNC);
+  if (t.pcm) return finish_call(c, B, t.samples, pcm, taps, nonfinite, rep, async);
+  return finish_call(c, B, t.samples, out, taps, nonfinite, rep, async);
 }
 
 // afs_synthesize: every utterance F frames, rows of T = (F - 1) * hop samples
@@ -869,6 +900,69 @@ afs_status afs_synthesize_ragged(afs_ctx *c, const afs_frame *frames, int64_t fs
   t.seeds = seeds, t.B = B, t.hop = hop;
   t.out = out, t.ostride = ostride, t.taps_out = taps_out;
   return synth_core(c, t, nonfinite, rep);
+}
+
+// what a _pcm call needs of its destination: the tree solver, rows of at least T int16 samples
+static afs_status pcm_check(afs_ctx *c, const char *fn, const int16_t *pcm, int64_t pstride, int64_t T) {
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!pcm || (reinterpret_cast<uintptr_t>(pcm) & 1))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: pcm is NULL or not int16-aligned", fn);
+  if (pstride < T)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: pcm_stride %lld below the longest utterance's %lld samples", fn,
+                (long long)pstride, (long long)T);
+  return AFS_OK;
+}
+
+afs_status afs_synthesize_pcm(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
+                              int32_t hop, int16_t *pcm, int64_t pstride, uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  const char *fn = "afs_synthesize_pcm";
+  if (!frames || B <= 0 || F < 2 || hop < 1)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, batch>0, num_frames>=2, hop>=1", fn);
+  Trajectories t;
+  t.frames = frames, t.fstride = t.F = F;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.ostride = (int64_t)(F - 1) * hop;
+  const afs_status s = pcm_check(c, fn, pcm, pstride, t.ostride);
+  if (s != AFS_OK) return s;
+  t.pcm = pcm, t.pstride = pstride;
+  t.samples = (int64_t)B * t.ostride;
+  return synth_core(c, t, nonfinite, rep);
+}
+
+afs_status afs_synthesize_ragged_pcm(afs_ctx *c, const afs_frame *frames, int64_t fstride, const int32_t *num_frames,
+                                     const uint32_t *seeds, int32_t B, int32_t hop, int16_t *pcm, int64_t pstride,
+                                     uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  const char *fn = "afs_synthesize_ragged_pcm";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!frames || B <= 0 || hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, batch>0, hop>=1", fn);
+  if (!num_frames || is_device_ptr(num_frames))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
+  Trajectories t;
+  for (int32_t u = 0; u < B; ++u) {
+    const int32_t F = num_frames[u];
+    if (F < 2 || F > fstride)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 2..frame_stride = %lld", fn, u, F,
+                  (long long)fstride);
+    t.F = std::max(t.F, F);
+    t.samples += (int64_t)(F - 1) * hop;
+  }
+  t.ostride = (int64_t)(t.F - 1) * hop;
+  const afs_status s = pcm_check(c, fn, pcm, pstride, t.ostride);
+  if (s != AFS_OK) return s;
+  t.frames = frames, t.fstride = fstride, t.num_frames = num_frames;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.pcm = pcm, t.pstride = pstride;
+  return synth_core(c, t, nonfinite, rep);
+}
+
+afs_status afs_memory_info_get(afs_ctx *c, afs_memory_info *info) {
+  if (!c || !info) return AFS_ERR_INVALID_ARGUMENT;
+  info->total_bytes = info->sample_buffer_bytes = 0;
+  for (const afs::DeviceBuf *b : c->device_bufs()) info->total_bytes += (int64_t)b->capacity();
+  for (const afs::DeviceBuf *b : c->sample_bufs()) info->sample_buffer_bytes += (int64_t)b->capacity();
+  return AFS_OK;
 }
 
 afs_status afs_section_currents(int32_t section, int32_t *in, int32_t out[2]) {
@@ -1085,9 +1179,10 @@ void afs_session_destroy(afs_session *s) {
 
 }  // extern "C"
 
-// afs_session_synthesize; taps_out: afs_session_synthesize_taps, else null
+// afs_session_synthesize; taps_out: afs_session_synthesize_taps, else null; pcm (out null):
+// afs_session_synthesize_pcm
 static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t n, double *out, double *taps_out,
-                               uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+                               int16_t *pcm, uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
   if (!s || !frames) return AFS_ERR_INVALID_ARGUMENT;
   afs_ctx *c = s->ctx;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1113,19 +1208,23 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
     if (rep) { std::memset(rep, 0, sizeof *rep); rep->kernel = c->cfg.solver; }
     return AFS_OK;
   }
-  if (!out) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize: out is NULL");
+  if (!out && !pcm) return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize: out is NULL");
   if (n < 1) n = 1;  // Synthesizer.cpp:543-546
-  const size_t out_bytes = (size_t)B * (size_t)n * sizeof(double);
+  const size_t out_bytes = (size_t)B * (size_t)n * sizeof(double), pcm_bytes = (size_t)B * (size_t)n * sizeof(int16_t);
   Staged<double> dout, dtaps;
+  Staged<int16_t> dpcm;
   afs_status st;
   if ((st = dout.stage(c, out, out_bytes, c->stage_out)) != AFS_OK) return st;
-  if (dout.host) HIP_TRY(c, s->hout.reserve(out_bytes));  // (back through the session's pinned buffer)
+  if ((st = dpcm.stage(c, pcm, pcm_bytes, c->stage_pcm)) != AFS_OK) return st;
+  // (back through the session's pinned buffer)
+  if (dout.host || dpcm.host) HIP_TRY(c, s->hout.reserve(dout.host ? out_bytes : pcm_bytes));
   if ((st = dtaps.stage(c, taps_out, out_bytes * (size_t)c->n_taps, c->stage_taps)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   SynthCall call;
   call.frames = pair, call.fstride = 2, call.rows = B;
   call.ntrans = 1, call.hop = n;
   call.out = dout.dev, call.ostride = n;
+  call.pcm = dpcm.dev, call.pstride = n;
   call.taps.out = dtaps.dev, call.taps.stride = n;
   call.ws = s->ws.data(), call.rng = s->rng.as<int32_t>(), call.lanes = s->tree_lanes.data();
   call.bp = s->bp, call.B = B, call.width = s->lanes;
@@ -1138,9 +1237,11 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   bool nf_sync = false;
   if ((st = nonfinite_report(c, s->ws.data(), s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
   if ((st = dout.copy_back(c, s->hout.data())) != AFS_OK) return st;
+  if ((st = dpcm.copy_back(c, s->hout.data())) != AFS_OK) return st;
   if ((st = dtaps.copy_back(c)) != AFS_OK) return st;
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a session call always waits: its audio is due now)
   if (dout.host) std::memcpy(out, s->hout.data(), out_bytes);
+  if (dpcm.host) std::memcpy(pcm, s->hout.data(), pcm_bytes);
   if (produced) *produced = n;
   return fill_report(c, rep, (int64_t)B * n);
 }
@@ -1149,7 +1250,18 @@ extern "C" {
 
 afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32_t n, double *out,
                                   uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
-  return session_core(s, frames, n, out, nullptr, nonfinite, produced, rep);
+  return session_core(s, frames, n, out, nullptr, nullptr, nonfinite, produced, rep);
+}
+
+// (one lane per utterance: no PCM form, as for the whole-trajectory calls; the latching first call
+// writes nothing and does not look at pcm)
+afs_status afs_session_synthesize_pcm(afs_session *s, const afs_frame *frames, int32_t n, int16_t *pcm,
+                                      uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  if (!tree(s->ctx)) return fail(s->ctx, AFS_ERR_UNSUPPORTED, "afs_session_synthesize_pcm: tree solver only");
+  if (s->latched && (!pcm || (reinterpret_cast<uintptr_t>(pcm) & 1)))
+    return fail(s->ctx, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize_pcm: pcm is NULL or not int16-aligned");
+  return session_core(s, frames, n, nullptr, nullptr, pcm, nonfinite, produced, rep);
 }
 
 // (the latching first call produces no samples and leaves taps_out alone, as it leaves out)
@@ -1158,7 +1270,7 @@ afs_status afs_session_synthesize_taps(afs_session *s, const afs_frame *frames, 
   if (!s) return AFS_ERR_INVALID_ARGUMENT;
   const afs_status st = taps_check(s->ctx, "afs_session_synthesize_taps", taps_out);
   if (st != AFS_OK) return st;
-  return session_core(s, frames, n, out, taps_out, nonfinite, produced, rep);
+  return session_core(s, frames, n, out, taps_out, nullptr, nonfinite, produced, rep);
 }
 
 afs_status afs_session_rng_draws(afs_session *s, int64_t *draws) {

@@ -30,6 +30,9 @@ struct afs_ctx {
   afs::DeviceBuf hops;       // tree solver, hops >= PLAN_HOP_MIN: hop records (tree_plan.h PlanHop)
   afs::DeviceBuf p25;        // tree solver: section 25's pressure per sample of a launch (K6's tone input)
   afs::DeviceBuf plan_work;  // hop mode: K5's work list (the hops decided sample by sample)
+  // the _pcm calls: the radiated flows of one launch, [B][window stride] doubles between K1 and K6 (as
+  // p25), and the staging of a host pcm (int16_t)
+  afs::DeviceBuf flow, stage_pcm;
   // the environment's switches (afs_create; include/afs.h lists them)
   bool plan_dense = false;             // AFS_PLAN_DENSE=1: dense records at every hop (A/B, tests)
   int64_t launch_cap = 65536;          // samples per K1 launch at most (AFS_LAUNCH_SAMPLES lowers it)
@@ -67,6 +70,14 @@ struct afs_ctx {
   size_t pev_used = 0;
   std::vector<Timed> timed;
   bool timed_overflow = false;
+  // afs_memory_info_get: every device buffer above, and those of them that hold one double per
+  // utterance-sample (of a launch: the windows; of a call: staged fp64 audio and taps, a shard's audio)
+  std::vector<const afs::DeviceBuf *> device_bufs() const {
+    return {&dev_tab, &ws, &rng, &tree_lanes, &stage_in, &stage_out, &stage_seeds, &tgt, &plan, &hops, &p25,
+            &plan_work, &flow, &stage_pcm, &keys, &sort_tmp, &order_buf, &stage_nf, &m_out, &m_pcm, &m_nf, &m_root,
+            &stage_taps, &ragged, &dcount};
+  }
+  std::vector<const afs::DeviceBuf *> sample_bufs() const { return {&flow, &p25, &stage_out, &stage_taps, &m_out}; }
 };
 
 struct afs_session {

@@ -157,6 +157,14 @@ hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out,
                               const double *p25, int64_t p25_stride, int skin, hipStream_t st,
                               const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0,
                               const int32_t *row_hops = nullptr, int hop = 0, int64_t s_begin = 0);
+// K6 of the _pcm calls: the same filters over the launch's flow and p25 windows (rows of win_stride
+// doubles, read only; K1 stored them with TreeArgs::out = flow, out_stride = p25_stride = win_stride),
+// the audio written as int16 (afs_audio.h sample_to_int16) to pcm[u * pcm_stride + i], i < n, and
+// nowhere else; pcm at any 2-byte alignment.  skip_claims, row_hops: as launch_tree_output.
+hipError_t launch_tree_output_pcm(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
+                                  int64_t n, int B, const double *p25, int skin, int16_t *pcm, int64_t pcm_stride,
+                                  hipStream_t st, const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0,
+                                  const int32_t *row_hops = nullptr, int hop = 0, int64_t s_begin = 0);
 // Load the tree kernels' and K5's code objects on the current device (afs_create: no code-object
 // load inside the first synthesis call).
 hipError_t preload_tree_kernels();

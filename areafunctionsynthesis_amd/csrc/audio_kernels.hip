@@ -15,14 +15,7 @@
 
 namespace afs {
 
-__host__ __device__ inline int16_t sample_to_int16(double x) {
-  if (x > 1.0) return 32767;
-  if (x < -1.0) return -32768;
-  if (!(x == x)) return 0;
-  return (int16_t)(int)(x * 32767.0);  // |x| <= 1: fits; truncation towards zero
-}
-
-namespace {
+namespace {  // (sample_to_int16: afs_audio.h)
 
 __global__ void to_int16_kernel(const double *__restrict__ in, int16_t *__restrict__ out, int64_t n) {
   const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;

@@ -93,6 +93,43 @@ __global__ void __launch_bounds__(64) tree_output_ragged_kernel(const Tables *ta
   else output_filter_run_t<false, 1>(X, tab->consts, o, (int)n, nullptr);
 }
 
+// K6 of the _pcm calls: the same filters over the launch's flow window (flow[u * win_stride + i], read
+// only; p25 likewise), the audio converted to int16 (sample_to_int16) on its way out to
+// pcm[u * pcm_stride + i], i < n -- the fp64 audio is never stored.  Rows of pcm may sit at any 2-byte
+// alignment (tree_core.h PcmPack).  Instantiations of the filter of their own (FORM 2, 3).
+__global__ void __launch_bounds__(64) tree_output_pcm_kernel(const Tables *tab, double *lds_state, const double *flow,
+                                                             int64_t win_stride, int64_t n, int B, const double *p25,
+                                                             int skin, const uint32_t *skip_claims, int64_t skip_cap,
+                                                             int16_t *pcm, int64_t pcm_stride) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  const double *f = flow + (int64_t)u * win_stride;
+  int16_t *o = pcm + (int64_t)u * pcm_stride;
+  if (p25 && skin) output_filter_run_pcm<true, 2>(X, tab->consts, f, (int)n, p25 + (int64_t)u * win_stride, o);
+  else output_filter_run_pcm<false, 2>(X, tab->consts, f, (int)n, nullptr, o);
+}
+// ... of a ragged _pcm call (as tree_output_ragged_kernel)
+__global__ void __launch_bounds__(64) tree_output_pcm_ragged_kernel(const Tables *tab, double *lds_state,
+                                                                    const double *flow, int64_t win_stride, int64_t n,
+                                                                    int B, const double *p25, int skin,
+                                                                    const uint32_t *skip_claims, int64_t skip_cap,
+                                                                    int16_t *pcm, int64_t pcm_stride,
+                                                                    const int32_t *row_hops, int hop, int64_t s_begin) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  const int64_t left = (int64_t)row_hops[u] * hop - s_begin;
+  n = left < n ? left : n;
+  if (n <= 0) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  const double *f = flow + (int64_t)u * win_stride;
+  int16_t *o = pcm + (int64_t)u * pcm_stride;
+  if (p25 && skin) output_filter_run_pcm<true, 3>(X, tab->consts, f, (int)n, p25 + (int64_t)u * win_stride, o);
+  else output_filter_run_pcm<false, 3>(X, tab->consts, f, (int)n, nullptr, o);
+}
+
 // seeds == nullptr: utterance u is seeded u + 1 (afs.h)
 template <int W>
 __global__ void tree_reset_kernel(Lane<W> *lanes, double *lds, int B, const uint32_t *seeds) {
@@ -182,6 +219,20 @@ hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out,
   else
     hipLaunchKernelGGL(tree_output_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, out, out_stride, n, B,
                        p25, p25_stride, skin, skip_claims, skip_cap);
+  return hipGetLastError();
+}
+
+hipError_t launch_tree_output_pcm(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
+                                  int64_t n, int B, const double *p25, int skin, int16_t *pcm, int64_t pcm_stride,
+                                  hipStream_t st, const uint32_t *skip_claims, int64_t skip_cap,
+                                  const int32_t *row_hops, int hop, int64_t s_begin) {
+  if (B <= 0 || n <= 0) return hipSuccess;
+  if (row_hops)
+    hipLaunchKernelGGL(tree_output_pcm_ragged_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, flow,
+                       win_stride, n, B, p25, skin, skip_claims, skip_cap, pcm, pcm_stride, row_hops, hop, s_begin);
+  else
+    hipLaunchKernelGGL(tree_output_pcm_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, flow, win_stride,
+                       n, B, p25, skin, skip_claims, skip_cap, pcm, pcm_stride);
   return hipGetLastError();
 }
 

@@ -36,6 +36,7 @@ using std::sqrt;
 using std::fma;
 #endif
 
+#include "afs_audio.h"
 #include "afs_model.h"
 #include "tree_plan.h"
 
@@ -2172,8 +2173,45 @@ AFS_HD inline double output_filter_one(double *X, const Consts &C, double flow) 
 // the output filter's chain of sample i (independent) overlap, instead of two runs back to back.
 // FORM: a tag only -- a second kernel of a file takes an instantiation of its own (tds_tree.hip, K6 of
 // the ragged calls), so that each kernel stays the one caller of its copy and is compiled as before.
-template <bool TONE, int FORM = 0>
-AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, int n, const double *p25) {
+// SINK: where sample t of the run goes, sink.put(t, sample), called once per sample in order of t
+// (OutInPlace: back over its flow; PcmPack: as int16 into the caller's row).
+struct OutInPlace {
+  double *o;
+  AFS_HD void put(int t, double smp) const { o[t] = smp; }
+};
+
+// The int16 samples of a run of n, sample_to_int16 of each, into pcm[0 .. n) -- a row of the caller's
+// at any 2-byte alignment -- and nothing outside it.  One thread writes one row, so 2-byte stores would
+// each touch a line of their own: the samples are collected in a 128-bit shift register (the oldest in
+// the lowest bits: the lowest address) and stored 16 bytes at a time whenever the row's address reaches
+// a 16-byte boundary; the samples before the first boundary and after the last go out one by one.
+struct PcmPack {
+  int16_t *pcm;
+  int head, tail;  // samples [head, tail) are stored in groups of 8 from the 16-byte aligned pcm + head
+  uint64_t lo = 0, hi = 0;
+  AFS_HD PcmPack(int16_t *p, int n) : pcm(p) {
+    const int h = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 1);
+    head = h < n ? h : n;
+    tail = head + (n - head) / 8 * 8;
+  }
+  AFS_HD void put(int t, double smp) {
+    const int16_t v = sample_to_int16(smp);
+    if (t < head || t >= tail) {
+      pcm[t] = v;
+      return;
+    }
+    lo = (lo >> 16) | (hi << 48);
+    hi = (hi >> 16) | ((uint64_t)(uint16_t)v << 48);
+    if (((t - head) & 7) == 7) {
+      const uint64_t w[2] = {lo, hi};
+      __builtin_memcpy(__builtin_assume_aligned(pcm + (t - 7), 16), w, 16);
+    }
+  }
+};
+
+template <bool TONE, int FORM, class SINK>
+AFS_HD inline void output_filter_run_to(double *X, const Consts &C, const double *o, int n, const double *p25,
+                                        SINK &sink) {
   // (not contracted into fmas: each product and sum rounds as in the reference, so the result does
   // not depend on where a run starts -- a session's per-call runs equal one run over the whole
   // trajectory bit for bit; with contraction the compiler may pair the terms differently in
@@ -2251,7 +2289,7 @@ AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, in
       gp[i] = TONE ? p25[q] : 0.0;
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[t0 + i] = step(i, f[i], fp[i]);
+    for (int i = 0; i < 8; ++i) sink.put(t0 + i, step(i, f[i], fp[i]));
     shift(8);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -2260,7 +2298,7 @@ AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, in
     }
   }
   for (int t = nb; t < n; ++t) {  // the last n % 8 samples
-    o[t] = step(0, o[t], TONE ? p25[t] : 0.0);
+    sink.put(t, step(0, o[t], TONE ? p25[t] : 0.0));
     shift(1);
   }
 #pragma unroll
@@ -2271,6 +2309,21 @@ AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, in
 #pragma unroll
     for (int k = 0; k < 4; ++k) { X[X_TONE + k] = tx[3 - k]; X[X_TONE + 4 + k] = ty[3 - k]; }
   }
+}
+
+// ... in place: o[0..n) holds the flows and receives the audio
+template <bool TONE, int FORM = 0>
+AFS_HD inline void output_filter_run_t(double *X, const Consts &C, double *o, int n, const double *p25) {
+  OutInPlace sink{o};
+  output_filter_run_to<TONE, FORM>(X, C, o, n, p25, sink);
+}
+// ... the PCM form (K6 of the _pcm calls): flow[0..n) and p25[0..n) are read only, the audio goes to
+// pcm[0..n) as int16 and exists as doubles in registers alone
+template <bool TONE, int FORM>
+AFS_HD inline void output_filter_run_pcm(double *X, const Consts &C, const double *flow, int n, const double *p25,
+                                         int16_t *pcm) {
+  PcmPack sink(pcm, n);
+  output_filter_run_to<TONE, FORM>(X, C, flow, n, p25, sink);
 }
 
 AFS_HD inline void output_filter_run(double *X, const Consts &C, double *o, int n) {

@@ -46,6 +46,29 @@ def _nbytes(x) -> int:
     return int(x.nbytes)
 
 
+def _pcm_rows(out, B: int):
+    """(address, row stride in samples) of the int16 destination ``out[B, width]`` of a PCM call: a
+    numpy array or torch tensor whose samples are adjacent within a row; the rows may be strided
+    (a slice of a wider buffer)."""
+    if len(out.shape) != 2 or int(out.shape[0]) != B:
+        raise ValueError("a PCM out must be int16 [B, samples]")
+    if isinstance(out, np.ndarray):
+        if out.dtype != np.int16:
+            raise ValueError("a PCM out must be int16")
+        inner, row = out.strides[1] // 2, out.strides[0] // 2
+        exact = out.strides[1] % 2 == 0 and out.strides[0] % 2 == 0
+        addr = int(out.ctypes.data)
+    else:
+        if "int16" not in str(out.dtype):
+            raise ValueError("a PCM out must be int16")
+        inner, row, exact = int(out.stride(1)), int(out.stride(0)), True
+        addr = int(out.data_ptr())
+    width = int(out.shape[1])
+    if not exact or (width > 1 and inner != 1) or (B > 1 and row < width):
+        raise ValueError("a PCM out needs adjacent samples in rows that do not overlap")
+    return addr, (row if B > 1 else max(row, width))
+
+
 class Context:
     """An afs_ctx: device + sampling rate + solver + options (TdsModel::Options)."""
 
@@ -119,15 +142,27 @@ class Context:
         _native.check(self._lib.afs_set_taps(self._h, arr, len(taps)), self._h, "afs_set_taps")
         self.n_taps = len(taps)
 
+    def memory_info(self) -> dict:
+        """afs_memory_info_get: the device memory the context holds now -- ``total_bytes``, and
+        ``sample_buffer_bytes``, the part holding one fp64 value per utterance-sample (the launch
+        windows, staged fp64 audio or taps)."""
+        m = _native.AfsMemoryInfo()
+        _native.check(self._lib.afs_memory_info_get(self._h, ctypes.byref(m)), self._h, "afs_memory_info_get")
+        return {"total_bytes": int(m.total_bytes), "sample_buffer_bytes": int(m.sample_buffer_bytes)}
+
     def synthesize(self, frames, hop: int, seeds=None, out=None, report: bool = False, nonfinite=None,
-                   taps=False, taps_out=None):
+                   taps=False, taps_out=None, pcm: bool = False):
         """frames[B, F] (FRAME_DTYPE array, or a uint8 torch tensor [B, F, 1072] on the GPU)
         -> audio[B, (F-1)*hop] float64.  ``seeds=None``: 1 .. B.  ``nonfinite``: optional uint8
         array / tensor of B flags (1 = the utterance's audio holds NaN/Inf); with ``report``
         the returned dict carries them under ``nonfinite`` too.  ``taps=True``: returns
         ``(audio, taps[B, n_taps, T])`` -- the taps of :meth:`set_taps` after every sample
         (``taps_out``: a numpy array or GPU tensor to receive them) -- and with ``report``
-        ``(audio, taps, report)``."""
+        ``(audio, taps, report)``.  ``pcm=True``: the audio as int16[B, T] (afs_synthesize_pcm: bit
+        for bit :meth:`to_int16` of the float64 audio, which is then never stored); ``out`` may be an
+        int16 numpy array or GPU tensor [B, T] with strided rows.  No taps with ``pcm``."""
+        if pcm and taps:
+            raise ValueError("the PCM calls have no taps")
         if isinstance(frames, np.ndarray):
             if frames.dtype != FRAME_DTYPE or frames.ndim != 2:
                 raise ValueError("frames must be a 2-D FRAME_DTYPE array [B, F]")
@@ -143,8 +178,12 @@ class Context:
         if isinstance(seeds, np.ndarray):
             seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         if out is None:
-            out = np.zeros((B, T), dtype=np.float64)
-        if _nbytes(out) != B * T * 8:
+            out = np.zeros((B, T), dtype=np.int16 if pcm else np.float64)
+        if pcm:
+            if tuple(out.shape) != (B, T):
+                raise ValueError("a PCM out must be int16 [B, (F-1)*hop]")
+            pcm_addr, pcm_stride = _pcm_rows(out, B)
+        elif _nbytes(out) != B * T * 8:
             raise ValueError("out must hold B*(F-1)*hop doubles")
         if nonfinite is None and report:
             nonfinite = np.zeros(B, dtype=np.uint8)
@@ -163,6 +202,10 @@ class Context:
                                                _vp(_addr(out)), _vp(_addr(taps_out)), _vp(_addr(nonfinite)),
                                                ctypes.byref(rep) if report else None)
             _native.check(st, self._h, "afs_synthesize_taps")
+        elif pcm:
+            st = self._lib.afs_synthesize_pcm(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop, _vp(pcm_addr),
+                                              pcm_stride, _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize_pcm")
         else:
             st = self._lib.afs_synthesize(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop,
                                           _vp(_addr(out)), _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
@@ -175,7 +218,7 @@ class Context:
         return res if len(res) > 1 else res[0]
 
     def synthesize_ragged(self, frames, num_frames, hop: int, seeds=None, out=None, report: bool = False,
-                          nonfinite=None, taps=False, taps_out=None):
+                          nonfinite=None, taps=False, taps_out=None, pcm: bool = False):
         """:meth:`synthesize` for utterances of different lengths in one call (tree solver).
         ``frames``: a ``[B, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[B, Fmax, 1072]`` of which
         utterance u plays the first ``num_frames[u]`` frames (the rest is never read), or a list of
@@ -184,7 +227,11 @@ class Context:
         valid samples in row u -- ``out_stride`` is the longest utterance's, or the row length of a
         given ``out`` -- then the taps ``[B, n_taps, out_stride]`` and the report as :meth:`synthesize`
         appends them.  Row u is bit for bit ``synthesize(frames[u:u+1, :num_frames[u]], hop)`` with
-        its seed.  Nothing is written past a row's end: an ``out`` allocated here is zero there."""
+        its seed.  Nothing is written past a row's end: an ``out`` allocated here is zero there.
+        ``pcm=True``: the audio as int16 (afs_synthesize_ragged_pcm; ``out``: int16 ``[B, out_stride]``,
+        numpy or GPU tensor, rows may be strided); no taps."""
+        if pcm and taps:
+            raise ValueError("the PCM calls have no taps")
         if isinstance(frames, (list, tuple)):
             rows = [np.ascontiguousarray(f, dtype=FRAME_DTYPE).reshape(-1) for f in frames]
             if num_frames is None:
@@ -213,11 +260,14 @@ class Context:
         if isinstance(seeds, np.ndarray):
             seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         if out is None:
-            out = np.zeros((B, max(int(lengths.max()), 0) if lengths is not None else 0), dtype=np.float64)
+            out = np.zeros((B, max(int(lengths.max()), 0) if lengths is not None else 0),
+                           dtype=np.int16 if pcm else np.float64)
         if tuple(out.shape)[:1] != (B,) or len(out.shape) != 2:
             raise ValueError("out must be [B, out_stride] doubles")
         ostride = int(out.shape[1])
-        if _nbytes(out) != B * ostride * 8:
+        if pcm:
+            pcm_addr, pcm_stride = _pcm_rows(out, B)
+        elif _nbytes(out) != B * ostride * 8:
             raise ValueError("out must be [B, out_stride] doubles")
         if nonfinite is None and report:
             nonfinite = np.zeros(B, dtype=np.uint8)
@@ -230,11 +280,17 @@ class Context:
             if nt and _nbytes(taps_out) != B * nt * ostride * 8:  # (no taps set: the library refuses the call)
                 raise ValueError("taps_out must hold B*n_taps*out_stride doubles")
         rep = _native.AfsReport()
-        st = self._lib.afs_synthesize_ragged(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
-                                             _vp(_addr(seeds)), B, hop, _vp(_addr(out)), ostride,
-                                             _vp(_addr(taps_out) if taps else 0), _vp(_addr(nonfinite)),
-                                             ctypes.byref(rep) if report else None)
-        _native.check(st, self._h, "afs_synthesize_ragged")
+        if pcm:
+            st = self._lib.afs_synthesize_ragged_pcm(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                     _vp(_addr(seeds)), B, hop, _vp(pcm_addr), pcm_stride,
+                                                     _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize_ragged_pcm")
+        else:
+            st = self._lib.afs_synthesize_ragged(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                 _vp(_addr(seeds)), B, hop, _vp(_addr(out)), ostride,
+                                                 _vp(_addr(taps_out) if taps else 0), _vp(_addr(nonfinite)),
+                                                 ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize_ragged")
         res = (out, lengths) + ((taps_out,) if taps else ())
         if report:
             res += ({"device_ms": rep.device_ms, "samples": rep.samples,
@@ -588,11 +644,21 @@ class Synthesizer:
         s = np.arange(1, self.batch + 1, dtype=np.uint32) if seeds is None else np.asarray(seeds, dtype=np.uint32)
         _native.check(self._lib.afs_session_reset(self._h, _vp(_addr(s))), self.ctx.handle, "afs_session_reset")
 
-    def synthesize_signal_tds(self, frames: np.ndarray, num_samples: int, taps: bool = False):
+    def synthesize_signal_tds(self, frames: np.ndarray, num_samples: int, taps: bool = False, pcm: bool = False):
         """``taps=True``: returns (audio, taps[batch, n_taps, produced]) with the context's taps
-        (:meth:`Context.set_taps`) after every sample."""
+        (:meth:`Context.set_taps`) after every sample.  ``pcm=True``: the audio as int16
+        (afs_session_synthesize_pcm: what Synthesizer::synthesizeSegment stores of each call); no taps."""
+        if pcm and taps:
+            raise ValueError("the PCM calls have no taps")
         fr = np.ascontiguousarray(np.broadcast_to(frames, (self.batch,)), dtype=FRAME_DTYPE)
         n = max(int(num_samples), 1)
+        if pcm:
+            out = np.zeros((self.batch, n), dtype=np.int16)
+            produced = ctypes.c_int32(0)
+            st = self._lib.afs_session_synthesize_pcm(self._h, _vp(_addr(fr)), int(num_samples), _vp(_addr(out)), None,
+                                                      ctypes.byref(produced), None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_pcm")
+            return out[:, : produced.value]
         out = np.zeros((self.batch, n), dtype=np.float64)
         produced = ctypes.c_int32(0)
         if taps:

@@ -333,6 +333,44 @@ afs_status afs_af_to_frames(afs_ctx *ctx, const double *params, int64_t n, afs_f
  * x < -1 -> -32768, NaN -> 0 (Synthesizer.cpp:955-973).  Host or device pointers. */
 afs_status afs_to_int16(afs_ctx *ctx, const double *samples, int64_t n, int16_t *out);
 
+/* ---- PCM output calls: the int16 audio without a call-long fp64 buffer ----------------------
+ * afs_synthesize, afs_synthesize_ragged and afs_session_synthesize delivering what
+ * Synthesizer::synthesizeSegment stores (Synthesizer.cpp:955-973): row u of pcm, pcm[u*pcm_stride + s],
+ * is bit for bit afs_to_int16 of the row the fp64 call returns for the same arguments, context and
+ * lane width (a NaN sample is 0); nonfinite, afs_rng_draws / afs_session_rng_draws and report->samples
+ * are the fp64 call's as well.  pcm is host or device memory at any int16 alignment, pcm_stride >= T
+ * (ragged: the longest T_u) in samples, and it reaches to the end of the last row's samples,
+ * (batch-1)*pcm_stride + T; nothing is written outside [u*pcm_stride, u*pcm_stride + T_u).  The session
+ * call takes pcm[batch][max(num_samples,1)]; its latching first call produces 0 samples and writes
+ * nothing.  PCM and fp64 calls may alternate on one session.
+ * The output stage converts each sample on its way out: the fp64 audio is never stored.  Between the
+ * synthesis kernel and the output stage the radiated flows cross a window of one launch's samples
+ * (batch x min(T, AFS_LAUNCH_SAMPLES, default 65536) doubles, next to the section-25 pressures' window
+ * of the same shape) that does not grow with T.  Still allocated per T: the frames (a host array's
+ * staging), the hop records of the call (544 B per utterance and hop) and, for a host pcm, its int16
+ * staging (2 B per sample; a host pcm with pcm_stride > T is uploaded first and copied back whole).  A
+ * device pcm does not wait under AFS_ASYNC.
+ * Tree solver only (AFS_ERR_UNSUPPORTED otherwise).  AFS_ERR_INVALID_ARGUMENT: a NULL or odd pcm,
+ * pcm_stride below T, and what the fp64 call refuses.  There is no _taps form. */
+afs_status afs_synthesize_pcm(afs_ctx *ctx, const afs_frame *frames, const uint32_t *seeds, int32_t batch,
+                              int32_t num_frames, int32_t hop, int16_t *pcm, int64_t pcm_stride,
+                              uint8_t *nonfinite, afs_report *report);
+afs_status afs_synthesize_ragged_pcm(afs_ctx *ctx, const afs_frame *frames, int64_t frame_stride,
+                                     const int32_t *num_frames, const uint32_t *seeds, int32_t batch, int32_t hop,
+                                     int16_t *pcm, int64_t pcm_stride, uint8_t *nonfinite, afs_report *report);
+afs_status afs_session_synthesize_pcm(afs_session *s, const afs_frame *frames, int32_t num_samples, int16_t *pcm,
+                                      uint8_t *nonfinite, int32_t *produced, afs_report *report);
+/* Diagnostics: the device memory the context holds now (its buffers grow on demand and are kept).
+ * total_bytes: all of it; sample_buffer_bytes: the part that holds one fp64 value per
+ * utterance-sample -- the flow and section-25 windows of a launch, a staged fp64 out or taps of a host
+ * caller, a shard's fp64 audio (afs_multi_synthesize).  A context that has only run PCM calls holds
+ * the two windows alone. */
+typedef struct afs_memory_info {
+  int64_t total_bytes;
+  int64_t sample_buffer_bytes;
+} afs_memory_info;
+afs_status afs_memory_info_get(afs_ctx *ctx, afs_memory_info *info);
+
 /* Synthesizer::playTargetSequence(targetShape, stationary_s, transition_s)
  * (Synthesizer.cpp:1299-1422).  The reference hard-codes f0_hz {100, 115, 105, 80} (:1311), the
  * 8000 dPa lung pressure of sensorDataToGlottisParams (:903) and takes the other glottis controls

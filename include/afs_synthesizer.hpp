@@ -125,6 +125,31 @@ class TdsVoices {
     return produced;
   }
 
+  // synthesizeSignalTds followed by what Synthesizer::synthesizeSegment does with its samples
+  // (Synthesizer.cpp:955-973): the call's audio as the int16 values of the audio ring, converted on
+  // the GPU (afs_session_synthesize_pcm).  Voice 0 (batch == 1); newSignal holds >= max(n, 1) shorts.
+  int synthesizeSignalTdsPcm(const TubeT *newTube, const double *newGlottisParams, int numNewSamples,
+                             short *newSignal) {
+    if (batch_ != 1) throw Error(AFS_ERR_INVALID_ARGUMENT, "single-voice call on a batched TdsVoices");
+    return synthesizeSignalTdsPcm(&newTube, &newGlottisParams, numNewSamples, &newSignal);
+  }
+
+  // ... all voices at once
+  int synthesizeSignalTdsPcm(const TubeT *const *newTubes, const double *const *newGlottisParams,
+                             int numNewSamples, short *const *newSignals) {
+    static_assert(sizeof(short) == sizeof(int16_t), "the audio ring's samples are 16 bits");
+    for (int b = 0; b < batch_; ++b) frames_[(size_t)b] = frame_from_tube(*newTubes[b], newGlottisParams[b]);
+    const int n = numNewSamples < 1 ? 1 : numNewSamples;
+    pcm_.resize((size_t)batch_ * (size_t)n);
+    int32_t produced = 0;
+    check(afs_session_synthesize_pcm(s_, frames_.data(), numNewSamples, pcm_.data(), nullptr, &produced, nullptr),
+          ctx_.get(), "afs_session_synthesize_pcm");
+    for (int b = 0; b < batch_; ++b)
+      if (newSignals[b] && produced > 0)
+        std::memcpy(newSignals[b], pcm_.data() + (size_t)b * (size_t)n, sizeof(int16_t) * (size_t)produced);
+    return produced;
+  }
+
   int batch() const { return batch_; }
 
  private:
@@ -133,6 +158,7 @@ class TdsVoices {
   afs_session *s_ = nullptr;
   std::vector<afs_frame> frames_;
   std::vector<double> out_;
+  std::vector<int16_t> pcm_;
 };
 
 }  // namespace afs
