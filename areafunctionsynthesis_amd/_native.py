@@ -44,6 +44,8 @@ EXPORTED = (
     "afs_set_taps", "afs_synthesize_taps", "afs_session_synthesize_taps", "afs_section_currents",
     "afs_synthesize_ragged",
     "afs_synthesize_pcm", "afs_synthesize_ragged_pcm", "afs_session_synthesize_pcm", "afs_memory_info_get",
+    "afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
+    "afs_session_latched",
 )
 
 
@@ -173,6 +175,15 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_session_synthesize_pcm.argtypes = [vp, vp, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                                ctypes.POINTER(AfsReport)]
     lib.afs_memory_info_get.argtypes = [vp, ctypes.POINTER(AfsMemoryInfo)]
+    lib.afs_session_restart_voices.argtypes = [vp, vp, vp, ctypes.c_int32]
+    lib.afs_session_synthesize_ragged.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, vp, ctypes.c_int64, vp,
+                                                  vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_session_synthesize_ragged_pcm.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, vp, ctypes.c_int64,
+                                                      vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_session_latched.argtypes = [vp, vp]
+    for name in ("afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
+                 "afs_session_latched"):
+        getattr(lib, name).restype = ctypes.c_int
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",
                  "afs_to_int16", "afs_play_target_sequences", "afs_rng_draws", "afs_session_rng_draws", "afs_plan_hop_words",

@@ -25,7 +25,7 @@ LIB = os.path.join(HERE, "libafs.so")
 ARCH = os.environ.get("AFS_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["afs_capi.cpp", "afs_comm.cpp", "afs_tables.cpp", "tds_lane.hip", "tds_tree.hip", "tds_plan.hip",
-           "af_kernels.hip", "audio_kernels.hip"]
+           "af_kernels.hip", "audio_kernels.hip", "session_kernels.hip"]
 # The phase profiler (tools/phase_prof): the tree kernel's body with cycle counters, linked with
 # the library's own objects of the kernels and their tables.
 PROF_DIR = os.path.join(ROOT, "tools", "phase_prof")

@@ -22,6 +22,7 @@
 #include "afs_ctx.h"
 #include "afs_model.h"
 #include "afs_ragged_order.h"
+#include "afs_session_kernels.h"
 #include "afs_tree.h"
 #include "afs_xcd_order.h"
 
@@ -628,7 +629,7 @@ afs_status afs_create(afs_ctx **out, const afs_config *cfg) {
   // the code objects of the kernels a synthesis call launches, loaded now rather than at their
   // first launch (which cost a real-time caller's first buffer ~35 ms)
   if (afs::preload_tree_kernels() != hipSuccess || afs::preload_plan_kernels() != hipSuccess ||
-      afs::preload_audio_kernels() != hipSuccess)
+      afs::preload_audio_kernels() != hipSuccess || afs::preload_session_kernels() != hipSuccess)
     return bail(AFS_ERR_HIP);
   if (hipEventCreateWithFlags(&ctx->ev_k5, hipEventDisableTiming) != hipSuccess) return bail(AFS_ERR_HIP);
   if (const char *e = std::getenv("AFS_PLAN_DENSE")) ctx->plan_dense = std::atoi(e) != 0;
@@ -1168,7 +1169,7 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds) {
   afs_status st = reset_state(c, s->ws.data(), s->rng.as<int32_t>(), s->tree_lanes.data(), s->bp, s->B,
                               seeds ? s->seeds.as<uint32_t>() : nullptr, s->lanes);
   if (st != AFS_OK) return st;
-  s->latched = false;
+  s->latch.assign((size_t)s->B, 0);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
@@ -1187,6 +1188,13 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   afs_ctx *c = s->ctx;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int B = s->B;
+  // (one latch state for all voices: everything these calls could see before the voices had lives of
+  // their own; the pool calls and afs_session_reset take a session from any state)
+  const bool latched = s->all_latched(true);
+  if (!latched && !s->all_latched(false))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT,
+                "afs_session_synthesize: the voices differ in latch state (afs_session_restart_voices, "
+                "afs_session_synthesize_ragged): use afs_session_synthesize_ragged or afs_session_reset");
   // (the kinds of the caller's pointers are probed on every call: a freed buffer's address may come
   // back as memory of the other kind; one pointer query is ~1 us beside a ~6 ms call)
   const bool in_dev = is_device_ptr(frames);
@@ -1197,12 +1205,12 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   }
   const hipMemcpyKind k = in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   // frames[u] -> pair[u][slot]
-  const int slot = s->latched ? 1 : 0;
+  const int slot = latched ? 1 : 0;
   afs_frame *pair = s->pair.as<afs_frame>();
   HIP_TRY(c, hipMemcpy2DAsync(pair + slot, 2 * sizeof(afs_frame), src, sizeof(afs_frame),
                               sizeof(afs_frame), B, k, c->stream));
-  if (!s->latched) {  // Synthesizer.cpp:522-532
-    s->latched = true;
+  if (!latched) {  // Synthesizer.cpp:522-532
+    s->latch.assign((size_t)B, 1);
     if (produced) *produced = 0;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (rep) { std::memset(rep, 0, sizeof *rep); rep->kernel = c->cfg.solver; }
@@ -1246,6 +1254,164 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
   return fill_report(c, rep, (int64_t)B * n);
 }
 
+// ---- the voice pool: per-voice frame counts, idle voices and restarts on a session ----
+
+// The launch layout of a pool call and its per-voice arrays on the device, sent as ragged_layout sends
+// a ragged call's (the context's pinned buffer, one upload on the stream, the event that guards its
+// reuse): block_end, the slot order and stand-ins of afs::pool_order, the transitions each voice plays
+// (K5's and K6's row_hops), then the frame counts and latch flags that launch_pool_rows reads.
+struct PoolArrays {
+  const int32_t *count = nullptr, *latched = nullptr;
+};
+static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *num_frames, const int32_t *trans, int upb,
+                              int hop, SynthCall *call, PoolArrays *pa) {
+  const int B = s->B;
+  const afs::RaggedOrder ro = afs::pool_order(trans, B, upb, hop);
+  const size_t slots = ro.order.size();
+  const size_t end_bytes = (size_t)ro.grid * sizeof(int64_t), slot_bytes = slots * sizeof(int32_t);
+  const size_t row_bytes = (size_t)B * sizeof(int32_t);
+  const size_t bytes = end_bytes + 2 * slot_bytes + 3 * row_bytes;
+  if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
+  HIP_TRY(c, c->ragged_host.reserve(bytes));
+  HIP_TRY(c, c->ragged.reserve(bytes));
+  char *h = c->ragged_host.as<char>(), *d = c->ragged.as<char>();
+  std::memcpy(h, ro.block_end.data(), end_bytes);
+  std::memcpy(h + end_bytes, ro.order.data(), slot_bytes);
+  std::memcpy(h + end_bytes + slot_bytes, ro.standin.data(), slot_bytes);
+  const size_t rows0 = end_bytes + 2 * slot_bytes;
+  std::memcpy(h + rows0, trans, row_bytes);
+  std::memcpy(h + rows0 + row_bytes, num_frames, row_bytes);
+  int32_t *lat = (int32_t *)(h + rows0 + 2 * row_bytes);
+  for (int u = 0; u < B; ++u) lat[u] = s->latch[(size_t)u] ? 1 : 0;
+  HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  call->ragged.block_end = (const int64_t *)d;
+  call->so.order = (const int32_t *)(d + end_bytes);
+  call->so.grid = ro.grid;
+  call->ragged.pad_standin = (const int32_t *)(d + end_bytes + slot_bytes);
+  call->ragged.row_hops = (const int32_t *)(d + rows0);
+  pa->count = (const int32_t *)(d + rows0 + row_bytes);
+  pa->latched = (const int32_t *)(d + rows0 + 2 * row_bytes);
+  return AFS_OK;
+}
+
+// afs_session_synthesize_ragged (taps_out or null), afs_session_synthesize_ragged_pcm (pcm, out null).
+// One SynthCall on the session's state over the call's frame rows (launch_pool_rows): voice u plays
+// trans[u] transitions -- its count, less one while it is unlatched -- ntrans the largest; K1's blocks
+// come from pool_order, so a voice without a transition is in no slot, K5 skips its row and K6 returns
+// at once: nothing of it is read or written.
+static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *frames, int64_t fstride,
+                            const int32_t *num_frames, int32_t hop, double *out, int64_t ostride, double *taps_out,
+                            int16_t *pcm, int64_t pstride, bool want_pcm, uint8_t *nonfinite, int32_t *produced,
+                            afs_report *rep) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  afs_ctx *c = s->ctx;
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (hop < 1 || fstride < 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need hop>=1, frame_stride>=0", fn);
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  if (!num_frames || is_device_ptr(num_frames))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
+  if (taps_out && c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
+  const int B = s->B;
+  std::vector<int32_t> trans((size_t)B);
+  int32_t ntrans = 0;
+  int64_t samples = 0;
+  bool any = false;
+  for (int u = 0; u < B; ++u) {
+    const int32_t n = num_frames[u];
+    if (n < 0 || n > fstride)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 0..frame_stride = %lld", fn, u, n,
+                  (long long)fstride);
+    trans[(size_t)u] = n == 0 ? 0 : (s->latch[(size_t)u] ? n : n - 1);
+    ntrans = std::max(ntrans, trans[(size_t)u]);
+    samples += (int64_t)trans[(size_t)u] * hop;
+    any |= n > 0;
+  }
+  const int64_t Tmax = (int64_t)ntrans * hop;
+  if (any && !frames) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: frames is NULL", fn);
+  if (want_pcm) {
+    if (pstride < Tmax)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: pcm_stride %lld below the %lld samples a voice produces", fn,
+                  (long long)pstride, (long long)Tmax);
+    if (Tmax > 0 && (!pcm || (reinterpret_cast<uintptr_t>(pcm) & 1)))
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: pcm is NULL or not int16-aligned", fn);
+  } else {
+    if (ostride < Tmax)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out_stride %lld below the %lld samples a voice produces", fn,
+                  (long long)ostride, (long long)Tmax);
+    if (Tmax > 0 && !out) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+  }
+  auto done = [&](int64_t n) {
+    for (int u = 0; u < B; ++u) {
+      if (produced) produced[u] = (int32_t)((int64_t)trans[(size_t)u] * hop);
+      if (num_frames[u] > 0) s->latch[(size_t)u] = 1;
+    }
+    return n;
+  };
+  if (!any) {  // every voice idle: nothing is queued
+    done(0);
+    if (rep) { std::memset(rep, 0, sizeof *rep); rep->kernel = c->cfg.solver; }
+    return AFS_OK;
+  }
+  afs_status st;
+  // the frames on the device, 16-byte aligned (a host array, or device memory at another alignment,
+  // through the context's staging buffer)
+  Frames fr;
+  const size_t fbytes = (size_t)B * (size_t)fstride * sizeof(afs_frame);
+  if (is_device_ptr(frames) && (reinterpret_cast<uintptr_t>(frames) & 15)) {
+    HIP_TRY(c, c->stage_in.reserve(fbytes));
+    HIP_TRY(c, hipMemcpyAsync(c->stage_in.data(), frames, fbytes, hipMemcpyDeviceToDevice, c->stream));
+    fr.dev = c->stage_in.as<const afs_frame>();
+  } else if ((st = frames_to_device(c, frames, (size_t)B * (size_t)fstride, &fr)) != AFS_OK) {
+    return st;
+  }
+  SynthCall call;
+  PoolArrays pa;
+  const int upb = s->lanes == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB;
+  call.so = plain_order(c);
+  if ((st = pool_layout(c, s, num_frames, trans.data(), upb, hop, &call, &pa)) != AFS_OK) return st;
+  const size_t had = c->pool_rows.capacity();
+  HIP_TRY(c, c->pool_rows.reserve((size_t)B * (size_t)(fstride + 1) * sizeof(afs_frame)));
+  // (a new block once, zeroed: K5 stages frame 0 of every row of a block's run, a voice's without a
+  // transition included, and never uses it)
+  if (c->pool_rows.capacity() != had) HIP_TRY(c, hipMemsetAsync(c->pool_rows.data(), 0, c->pool_rows.capacity(), c->stream));
+  afs_frame *rows = c->pool_rows.as<afs_frame>();
+  HIP_TRY(c, afs::launch_pool_rows(fr.dev, fstride, pa.count, pa.latched, B, rows, s->pair.as<afs_frame>(), c->stream));
+  if (ntrans == 0) {  // the voices that got frames only latch: no synthesis kernel runs
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    done(0);
+    if (rep) { std::memset(rep, 0, sizeof *rep); rep->kernel = c->cfg.solver; }
+    return AFS_OK;
+  }
+  // (a host out, taps_out or pcm goes up first and comes back whole: what lies outside the samples a
+  // voice produces is the caller's)
+  Staged<double> dout, dtaps;
+  Staged<int16_t> dpcm;
+  const size_t out_bytes = (size_t)B * (size_t)ostride * sizeof(double);
+  if ((st = dout.stage(c, out, out_bytes, c->stage_out, true)) != AFS_OK) return st;
+  if ((st = dtaps.stage(c, taps_out, out_bytes * (size_t)c->n_taps, c->stage_taps, true)) != AFS_OK) return st;
+  const size_t pcm_bytes = ((size_t)(B - 1) * (size_t)pstride + (size_t)Tmax) * sizeof(int16_t);
+  if ((st = dpcm.stage(c, pcm, pcm_bytes, c->stage_pcm, true)) != AFS_OK) return st;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  call.frames = rows, call.fstride = fstride + 1, call.rows = B;
+  call.ntrans = ntrans, call.hop = hop;
+  call.out = dout.dev, call.ostride = ostride;
+  call.pcm = dpcm.dev, call.pstride = pstride;
+  call.taps.out = dtaps.dev, call.taps.stride = ostride;
+  call.ws = s->ws.data(), call.rng = s->rng.as<int32_t>(), call.lanes = s->tree_lanes.data();
+  call.bp = s->bp, call.B = B, call.width = s->lanes;
+  if ((st = run_call(c, call)) != AFS_OK) return st;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  bool nf_sync = false;
+  if ((st = nonfinite_report(c, s->ws.data(), s->bp, B, nonfinite, rep != nullptr, &nf_sync)) != AFS_OK) return st;
+  if ((st = dout.copy_back(c)) != AFS_OK) return st;
+  if ((st = dpcm.copy_back(c)) != AFS_OK) return st;
+  if ((st = dtaps.copy_back(c)) != AFS_OK) return st;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a session call always waits: its audio is due now)
+  return fill_report(c, rep, done(samples));
+}
+
 extern "C" {
 
 afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32_t n, double *out,
@@ -1259,7 +1425,7 @@ afs_status afs_session_synthesize_pcm(afs_session *s, const afs_frame *frames, i
                                       uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
   if (!s) return AFS_ERR_INVALID_ARGUMENT;
   if (!tree(s->ctx)) return fail(s->ctx, AFS_ERR_UNSUPPORTED, "afs_session_synthesize_pcm: tree solver only");
-  if (s->latched && (!pcm || (reinterpret_cast<uintptr_t>(pcm) & 1)))
+  if (s->all_latched(true) && (!pcm || (reinterpret_cast<uintptr_t>(pcm) & 1)))
     return fail(s->ctx, AFS_ERR_INVALID_ARGUMENT, "afs_session_synthesize_pcm: pcm is NULL or not int16-aligned");
   return session_core(s, frames, n, nullptr, nullptr, pcm, nonfinite, produced, rep);
 }
@@ -1278,6 +1444,61 @@ afs_status afs_session_rng_draws(afs_session *s, int64_t *draws) {
   afs_ctx *c = s->ctx;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   return draws_of(c, s->ws.data(), s->B, draws);
+}
+
+afs_status afs_session_restart_voices(afs_session *s, const int32_t *voices, const uint32_t *seeds, int32_t n) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  afs_ctx *c = s->ctx;
+  const char *fn = "afs_session_restart_voices";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (n < 0 || (n > 0 && !voices)) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need n >= 0 voices", fn);
+  if (n == 0) return AFS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  if (is_device_ptr(voices) || (seeds && is_device_ptr(seeds)))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: voices and seeds are host arrays", fn);
+  std::vector<uint8_t> listed((size_t)s->B, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t v = voices[i];
+    if (v < 0 || v >= s->B) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: voices[%d] = %d outside 0..%d", fn, i, v, s->B - 1);
+    if (listed[(size_t)v]) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: voice %d listed twice", fn, v);
+    listed[(size_t)v] = 1;
+  }
+  // the two lists through the context's pinned buffer, as a pool call's arrays (pool_layout)
+  const size_t lb = (size_t)n * sizeof(int32_t), bytes = seeds ? 2 * lb : lb;
+  if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
+  HIP_TRY(c, c->ragged_host.reserve(bytes));
+  HIP_TRY(c, c->pool_list.reserve(bytes));
+  char *h = c->ragged_host.as<char>(), *d = c->pool_list.as<char>();
+  std::memcpy(h, voices, lb);
+  if (seeds) std::memcpy(h + lb, seeds, lb);
+  HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  HIP_TRY(c, afs::launch_voice_reset(s->tree_lanes.data(), s->ws.as<double>(), (const int32_t *)d,
+                                     seeds ? (const uint32_t *)(d + lb) : nullptr, n, s->lanes, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int32_t i = 0; i < n; ++i) s->latch[(size_t)voices[i]] = 0;
+  return AFS_OK;
+}
+
+afs_status afs_session_latched(afs_session *s, uint8_t *flags) {
+  if (!s || !flags) return AFS_ERR_INVALID_ARGUMENT;
+  for (int u = 0; u < s->B; ++u) flags[u] = s->latch[(size_t)u] ? 1 : 0;
+  return AFS_OK;
+}
+
+afs_status afs_session_synthesize_ragged(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                         const int32_t *num_frames, int32_t hop, double *out, int64_t out_stride,
+                                         double *taps_out, uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+  return pool_core(s, "afs_session_synthesize_ragged", frames, frame_stride, num_frames, hop, out, out_stride, taps_out,
+                   nullptr, 0, false, nonfinite, produced, rep);
+}
+
+afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                             const int32_t *num_frames, int32_t hop, int16_t *pcm, int64_t pcm_stride,
+                                             uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
+  return pool_core(s, "afs_session_synthesize_ragged_pcm", frames, frame_stride, num_frames, hop, nullptr, 0, nullptr,
+                   pcm, pcm_stride, true, nonfinite, produced, rep);
 }
 
 afs_status afs_af_to_frames(afs_ctx *c, const double *params, int64_t n, afs_frame *frames) {

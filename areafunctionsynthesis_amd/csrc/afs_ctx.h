@@ -59,6 +59,10 @@ struct afs_ctx {
   afs::DeviceBuf ragged;
   afs::PinnedBuf ragged_host;
   hipEvent_t ev_ragged = nullptr;
+  // afs_session_synthesize_ragged: the frame rows of one pool call, [B][frame_stride + 1] (session_kernels.hip;
+  // the call's own, nothing in it outlives the call -- the latched frames stay in the session's pair), and
+  // the voice and seed lists of afs_session_restart_voices
+  afs::DeviceBuf pool_rows, pool_list;
   int32_t last_B = 0;        // batch of the last whole-trajectory call (afs_rng_draws)
   afs::DeviceBuf dcount;  // int32_t: the non-finite utterances of a call
   afs::PinnedBuf hcount;  // pinned host copy of dcount
@@ -75,7 +79,7 @@ struct afs_ctx {
   std::vector<const afs::DeviceBuf *> device_bufs() const {
     return {&dev_tab, &ws, &rng, &tree_lanes, &stage_in, &stage_out, &stage_seeds, &tgt, &plan, &hops, &p25,
             &plan_work, &flow, &stage_pcm, &keys, &sort_tmp, &order_buf, &stage_nf, &m_out, &m_pcm, &m_nf, &m_root,
-            &stage_taps, &ragged, &dcount};
+            &stage_taps, &ragged, &dcount, &pool_rows, &pool_list};
   }
   std::vector<const afs::DeviceBuf *> sample_bufs() const { return {&flow, &p25, &stage_out, &stage_taps, &m_out}; }
 };
@@ -90,7 +94,14 @@ struct afs_session {
   int lanes = 16;             // tree solver: lanes per utterance (fixed at creation)
   afs::DeviceBuf pair;        // afs_frame [B][2]: previous frame, new frame
   afs::DeviceBuf seeds;       // device copy (uint32_t)
-  bool latched = false;
+  // per voice: whether pair[u][0] holds its latched frame (the first frame after create / reset /
+  // afs_session_restart_voices only latches).  The lock-step calls need one state for all voices.
+  std::vector<uint8_t> latch;
+  bool all_latched(bool v) const {
+    for (uint8_t x : latch)
+      if ((x != 0) != v) return false;
+    return true;
+  }
   // pinned staging of host frames (afs_frame) and host output (double): a real-time caller's
   // per-call copies go through these instead of pageable memory
   afs::PinnedBuf hframes, hout;

@@ -54,4 +54,37 @@ inline RaggedOrder ragged_order(const int32_t *num_frames, int B, int upb, int h
   return r;
 }
 
+// K1's launch layout of a session pool call (afs_session_synthesize_ragged): voice u plays
+// transitions[u] frame transitions of `hop` samples, and a voice with none -- idle, or one that only
+// latches its first frame -- takes no slot at all: K1 never sees it.  The live voices are laid out as
+// ragged_order lays out utterances (grouped by length in whole blocks, longest first, call order
+// inside a group, a padding slot reading the first live voice of its own block); a padding slot holds
+// B.  block_end[block] = transitions x hop.  No live voice: grid 0, nothing to launch.  Equal
+// non-zero lengths give the identity order.
+inline RaggedOrder pool_order(const int32_t *transitions, int B, int upb, int hop) {
+  RaggedOrder r;
+  if (B <= 0 || upb <= 0) return r;
+  std::vector<int32_t> idx;
+  for (int u = 0; u < B; ++u)
+    if (transitions[u] > 0) idx.push_back(u);
+  const int L = (int)idx.size();
+  std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return transitions[a] > transitions[b]; });
+  for (int q0 = 0; q0 < L;) {
+    int q1 = q0;
+    while (q1 < L && transitions[idx[(size_t)q1]] == transitions[idx[(size_t)q0]]) ++q1;  // one length: idx[q0 .. q1)
+    for (int q = q0; q < q1; q += upb) {
+      const int32_t first = idx[(size_t)q];
+      for (int g = 0; g < upb; ++g) {
+        const bool live = q + g < q1;
+        r.order.push_back(live ? idx[(size_t)(q + g)] : B);
+        r.standin.push_back(live ? idx[(size_t)(q + g)] : first);
+      }
+      r.block_end.push_back((int64_t)transitions[first] * hop);
+    }
+    q0 = q1;
+  }
+  r.grid = (int)r.block_end.size();
+  return r;
+}
+
 }  // namespace afs

@@ -1,0 +1,33 @@
+// afs_session_kernels.h -- the per-voice lifecycle of a session's voice pool (session_kernels.hip;
+// afs_session_restart_voices, afs_session_synthesize_ragged): the reset of listed voices and the frame
+// rows of a pool call.  The synthesis kernels themselves (tds_tree.hip, tds_plan.hip) know nothing of it.
+#pragma once
+
+#include <cstdint>
+
+#include <hip/hip_runtime.h>
+
+#include "afs_model.h"
+
+namespace afs {
+
+// tree_reset_kernel (tds_tree.hip) over a list: voice voices[i] (n distinct voices of the session's
+// state, `lanes` lanes each) gets fresh lane state and a fresh LDS image seeded seeds[i], or
+// voices[i] + 1 when seeds is null.  One thread per (listed voice, lane); nothing else is touched.
+hipError_t launch_voice_reset(void *lane_state, double *lds_state, const int32_t *voices, const uint32_t *seeds, int n,
+                              int lanes, hipStream_t st);
+
+// The frame rows of a pool call.  Voice u was given count[u] frames, frames[u * frame_stride + k], and
+// is latched on pair[u * 2] when latched[u] != 0.  Its row, rows[u * (frame_stride + 1) + j], becomes
+//   latched:   [latch, f_0 .. f_{c-1}]      unlatched:   [f_0 .. f_{c-1}]
+// and pair[u * 2] the new latch f_{c-1} (the old one is read before it is overwritten: by the same
+// wave, load before store).  count[u] == 0: nothing of voice u is read or written.  No frame at or past
+// count[u] is read.  One wave per frame of a row, its 67 16-byte vectors spread over the lanes;
+// frames, rows and pair are 16-byte aligned.
+hipError_t launch_pool_rows(const afs_frame *frames, int64_t frame_stride, const int32_t *count,
+                            const int32_t *latched, int B, afs_frame *rows, afs_frame *pair, hipStream_t st);
+
+// load the code object on the current device (afs_create; see afs_tree.h)
+hipError_t preload_session_kernels();
+
+}  // namespace afs

@@ -6,6 +6,9 @@
   an ``afs_session`` whose state stays on the GPU.
 * :meth:`Context.synthesize` -- whole trajectories (latch frame 0, then ``F-1`` calls of
   ``hop`` samples) for ``B`` utterances in one go.
+* :meth:`Context.synthesize_stream` -- continuous batching: a corpus streamed through a pool of
+  voices (:meth:`Synthesizer.synthesize_frames`, :meth:`Synthesizer.restart`), a few frames per
+  voice and call.
 * :meth:`Context.play_target_sequences` -- ``Synthesizer::playTargetSequence``
   (``src/Backend/Synthesizer.cpp:1299-1422``) for ``B`` utterances: four target shapes each,
   per-sample area-function tubes built on the GPU.
@@ -297,6 +300,24 @@ class Context:
                      "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
                      "nonfinite": nonfinite},)
         return res
+
+    def synthesize_stream(self, utterances, hop: int, slots: int, chunk_frames: int, seeds=None, pcm: bool = True,
+                          finished=None):
+        """Continuous batching (tree solver): a generator over ``utterances``, an iterable of
+        per-utterance FRAME_DTYPE arrays of at least 2 frames, yielding ``(index, audio)`` as each one
+        ends -- int16 with ``pcm``, else float64; ``(F-1)*hop`` samples.  A session of ``slots`` voices
+        plays up to ``chunk_frames`` frames of every live utterance per step (:func:`stream_utterances`),
+        so the frames and audio held at a time are slots x chunk_frames, whatever the corpus holds.
+        ``seeds``: indexable by utterance (None: index + 1).  Utterance i's audio is bit for bit
+        ``synthesize(utterances[i][None], hop, seeds=[seed_i])`` on a context of the session's lane
+        width.  ``finished(index, slot, session, nonfinite)``: called when an utterance ends, before its
+        voice is restarted."""
+        session = Synthesizer(self, int(slots))
+        try:
+            yield from stream_utterances(session, utterances, hop, chunk_frames, seeds=seeds, pcm=pcm,
+                                         finished=finished)
+        finally:
+            session.close()
 
     def noise_plans(self, frames: np.ndarray, hop: int, s_begin: int = 0, s_end: Optional[int] = None) -> np.ndarray:
         """Diagnostics (tree solver): the noise-source plan records K5 computes for samples
@@ -672,6 +693,104 @@ class Synthesizer:
         _native.check(st, self.ctx.handle, "afs_session_synthesize")
         return out[:, : produced.value]
 
+    def restart(self, voices, seeds=None) -> None:
+        """afs_session_restart_voices: the listed voices (distinct indices) get fresh state -- what
+        :meth:`reset` gives every voice -- and are unlatched; no other voice changes.  ``seeds``: one per
+        listed voice (None: voice v is seeded v + 1)."""
+        v = np.ascontiguousarray(voices, dtype=np.int32).reshape(-1)
+        s = None
+        if seeds is not None:
+            s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+            if s.shape != v.shape:
+                raise ValueError("one seed per listed voice")
+        _native.check(self._lib.afs_session_restart_voices(self._h, _vp(_addr(v)), _vp(_addr(s)), int(v.size)),
+                      self.ctx.handle, "afs_session_restart_voices")
+
+    @property
+    def latched(self) -> np.ndarray:
+        """uint8[batch]: 1 for the voices that hold a latched frame (the next frame plays a transition)."""
+        f = np.zeros(self.batch, dtype=np.uint8)
+        _native.check(self._lib.afs_session_latched(self._h, _vp(_addr(f))), self.ctx.handle, "afs_session_latched")
+        return f
+
+    def synthesize_frames(self, frames, num_frames, hop: int, out=None, taps: bool = False, taps_out=None,
+                          pcm: bool = False, report: bool = False):
+        """afs_session_synthesize_ragged: every voice plays its own number of frames in one call.
+        ``frames``: a ``[batch, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[batch, Fmax, 1072]`` of
+        which voice u plays the first ``num_frames[u]`` (the rest is never read), or a list of per-voice
+        FRAME_DTYPE arrays (``num_frames=None``: their lengths; an empty array: the voice is idle).  A
+        voice with count 0 is idle: nothing of it is read or written.  An unlatched voice latches its
+        first frame and plays the others as transitions of ``hop`` samples, a latched one plays every
+        frame.  Returns ``(audio[batch, out_stride], produced[batch])`` -- ``out_stride`` is the largest
+        ``produced``, or the row length of a given ``out`` (numpy or GPU tensor; nothing is written at or
+        past ``produced[u]`` in row u) -- then the taps ``[batch, n_taps, out_stride]`` and the report as
+        :meth:`Context.synthesize_ragged` appends them.  ``pcm=True``: int16 audio
+        (afs_session_synthesize_ragged_pcm; ``out``'s rows may be strided); no taps."""
+        if pcm and taps:
+            raise ValueError("the PCM calls have no taps")
+        B = self.batch
+        if isinstance(frames, (list, tuple)):
+            rows = [np.ascontiguousarray(f, dtype=FRAME_DTYPE).reshape(-1) for f in frames]
+            if num_frames is None:
+                num_frames = [len(r) for r in rows]
+            padded = np.zeros((len(rows), max([len(r) for r in rows] + [1])), dtype=FRAME_DTYPE)
+            for u, r in enumerate(rows):
+                padded[u, : len(r)] = r
+            frames = padded
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != FRAME_DTYPE or frames.ndim != 2 or frames.shape[0] != B:
+                raise ValueError("frames must be a 2-D FRAME_DTYPE array [batch, Fmax]")
+            fstride = frames.shape[1]
+            frames = np.ascontiguousarray(frames)
+        else:
+            fstride = int(frames.shape[1])
+            if int(frames.shape[0]) != B or _nbytes(frames) != B * fstride * FRAME_DTYPE.itemsize:
+                raise ValueError("device frames must hold batch*Fmax*1072 bytes")
+        counts = None
+        produced = np.zeros(B, dtype=np.int32)
+        if num_frames is not None:  # (a host array: the library builds the launch layout from it)
+            counts = np.ascontiguousarray(num_frames, dtype=np.int32)
+            if counts.shape != (B,):
+                raise ValueError("num_frames must hold batch counts")
+        if out is None:
+            width = 0
+            if counts is not None:
+                width = int(np.where(counts > 0, counts - 1 + self.latched.astype(np.int32), 0).max()) * hop
+            out = np.zeros((B, max(width, 0)), dtype=np.int16 if pcm else np.float64)
+        if len(out.shape) != 2 or int(out.shape[0]) != B:
+            raise ValueError("out must be [batch, out_stride]")
+        ostride = int(out.shape[1])
+        if pcm:
+            pcm_addr, pcm_stride = _pcm_rows(out, B)
+        elif _nbytes(out) != B * ostride * 8:
+            raise ValueError("out must be [batch, out_stride] doubles")
+        nonfinite = np.zeros(B, dtype=np.uint8) if report else None
+        if taps:
+            nt = getattr(self.ctx, "n_taps", 0)
+            if taps_out is None:
+                taps_out = np.zeros((B, nt, ostride), dtype=np.float64)
+            if nt and _nbytes(taps_out) != B * nt * ostride * 8:  # (no taps set: the library refuses the call)
+                raise ValueError("taps_out must hold batch*n_taps*out_stride doubles")
+        rep = _native.AfsReport()
+        if pcm:
+            st = self._lib.afs_session_synthesize_ragged_pcm(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                             int(hop), _vp(pcm_addr if ostride else 0), pcm_stride,
+                                                             _vp(_addr(nonfinite)), _vp(_addr(produced)),
+                                                             ctypes.byref(rep) if report else None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_ragged_pcm")
+        else:
+            st = self._lib.afs_session_synthesize_ragged(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                         int(hop), _vp(_addr(out) if ostride else 0), ostride,
+                                                         _vp(_addr(taps_out) if taps else 0), _vp(_addr(nonfinite)),
+                                                         _vp(_addr(produced)), ctypes.byref(rep) if report else None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_ragged")
+        res = (out, produced) + ((taps_out,) if taps else ())
+        if report:
+            res += ({"device_ms": rep.device_ms, "samples": rep.samples,
+                     "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                     "nonfinite": nonfinite},)
+        return res
+
     def rng_draws(self) -> np.ndarray:
         """rand() calls of every voice since construction / the last reset (tree solver)."""
         d = np.zeros(self.batch, dtype=np.int64)
@@ -692,3 +811,68 @@ class Synthesizer:
             self.close()
         except Exception:
             pass
+
+
+def stream_utterances(session, utterances, hop: int, chunk_frames: int, seeds=None, pcm: bool = True, finished=None):
+    """The continuous-batching scheduler behind :meth:`Context.synthesize_stream`, written against
+    what it needs of a session: ``batch``, ``restart(voices, seeds)`` and ``synthesize_frames(frames,
+    num_frames, hop, out=, pcm=, report=True) -> (audio, produced, report)``.
+
+    Every step, each empty voice takes the next utterance of the corpus (and is restarted with its
+    seed), every live voice is given up to ``chunk_frames`` of its remaining frames, and a voice without
+    an utterance -- the corpus is dry -- runs idle with count 0.  An utterance whose last frame has
+    played is yielded as ``(index, audio)``; its voice starts the next utterance in the following step."""
+    B, hop, chunk = int(session.batch), int(hop), int(chunk_frames)
+    if chunk < 1 or hop < 1:
+        raise ValueError("chunk_frames and hop must be at least 1")
+    corpus = enumerate(utterances)
+    index = [-1] * B            # the utterance a voice plays, -1: none
+    frames = [None] * B         # its frames, the next one to supply, its audio and the samples it has
+    pos, audio, have = [0] * B, [None] * B, [0] * B
+    rows = np.zeros((B, chunk), dtype=FRAME_DTYPE)
+    out = np.zeros((B, chunk * hop), dtype=np.int16 if pcm else np.float64)
+    dry = False
+    while True:
+        started, start_seeds = [], []
+        for u in range(B):
+            if index[u] >= 0 or dry:
+                continue
+            nxt = next(corpus, None)
+            if nxt is None:
+                dry = True
+                continue
+            i, fr = nxt
+            fr = np.ascontiguousarray(fr, dtype=FRAME_DTYPE).reshape(-1)
+            if len(fr) < 2:
+                raise ValueError(f"utterance {i} has {len(fr)} frames: at least 2 (one transition)")
+            index[u], frames[u], pos[u], have[u] = i, fr, 0, 0
+            audio[u] = np.zeros((len(fr) - 1) * hop, dtype=out.dtype)
+            started.append(u)
+            start_seeds.append(i + 1 if seeds is None else int(seeds[i]))
+        if started:
+            session.restart(started, start_seeds)
+        if all(i < 0 for i in index):
+            return
+        counts = np.zeros(B, dtype=np.int32)
+        for u in range(B):
+            if index[u] >= 0:
+                n = min(chunk, len(frames[u]) - pos[u])
+                rows[u, :n] = frames[u][pos[u]:pos[u] + n]
+                counts[u] = n
+        res = session.synthesize_frames(rows, counts, hop, out=out, pcm=pcm, report=True)
+        produced, rep = res[1], res[-1]
+        for u in range(B):
+            if index[u] < 0:
+                continue
+            n = int(produced[u])
+            audio[u][have[u]:have[u] + n] = out[u, :n]
+            have[u] += n
+            pos[u] += int(counts[u])
+            if pos[u] == len(frames[u]):
+                if have[u] != len(audio[u]):
+                    raise RuntimeError(f"utterance {index[u]}: {have[u]} of {len(audio[u])} samples produced")
+                if finished is not None:
+                    finished(index[u], u, session, int(rep["nonfinite"][u]))
+                done = (index[u], audio[u])
+                index[u], frames[u], audio[u] = -1, None, None
+                yield done

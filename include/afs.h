@@ -290,6 +290,51 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds);
 afs_status afs_session_rng_draws(afs_session *s, int64_t *draws);
 void afs_session_destroy(afs_session *s);
 
+/* ---- Voice pools: per-voice frame counts, idle voices and restarts on a session --------------
+ * Continuous batching: keep the session's B voices busy, feed each a few frames per call, and when a
+ * voice's utterance ends give that voice a fresh state and seed while the others carry on.  Memory is
+ * bounded by voices x frames per call instead of corpus x length.  Tree solver only (else
+ * AFS_ERR_UNSUPPORTED).
+ *
+ * afs_session_restart_voices: voices[n] (distinct, 0 <= v < batch) and seeds[n] are HOST arrays;
+ * seeds == NULL seeds voice v with v + 1.  Each listed voice gets what afs_session_reset gives every
+ * voice -- fresh lane state, a fresh output and tone filter state, non-finite flag, rand() state and
+ * draw count -- and is unlatched.  No byte of any other voice's state changes.
+ *
+ * afs_session_synthesize_ragged: frames[batch][frame_stride] (host or device), num_frames[batch] a HOST
+ * array, produced[batch] a host output (or NULL).  With c = num_frames[u], voice u
+ *   c == 0 (idle)          no frame, no state and no output byte of voice u is read or written; 0 samples
+ *   unlatched, c >= 1      frame 0 latches (Synthesizer.cpp:522-532), frames 1 .. c-1 play as transitions
+ *                          of hop samples: (c-1)*hop samples
+ *   latched, c >= 1        frames 0 .. c-1 play as c transitions from the latched frame: c*hop samples
+ * and a voice with c >= 1 is afterwards latched on its last supplied frame.  Frames at or past c are
+ * never read, samples at or past produced[u] in row out[u*out_stride ..] are never written (a host out,
+ * taps_out or pcm is staged: uploaded, written and copied back whole).  taps_out: NULL, or
+ * [batch][n_taps][out_stride] with the context's tap list.  nonfinite and report->samples (the sum of
+ * produced) as afs_synthesize_ragged; hop may differ from call to call; the call waits for its audio as
+ * every session call does.  A voice fed its utterance in pieces produces, bit for bit, the row, tap
+ * rows, rand() count and non-finite flag of afs_synthesize on that utterance alone with its seed (same
+ * lane width).  When no voice has a transition to play (all idle, or only latching) no synthesis kernel
+ * is launched, produced is all 0 and the call returns AFS_OK.
+ * afs_session_synthesize_ragged_pcm: the same with int16 rows pcm[u*pcm_stride ..] (as the _pcm calls
+ * above the conversion of the fp64 row, bit for bit; no taps).
+ * AFS_ERR_INVALID_ARGUMENT: a count outside 0..frame_stride, a NULL num_frames, hop < 1, out_stride or
+ * pcm_stride below the largest produced, a NULL out / pcm (or an odd pcm) when a voice produces samples,
+ * taps_out without a tap list, a voice index out of range or listed twice.
+ *
+ * afs_session_latched: flags[batch] host bytes, 1 for a latched voice.
+ * afs_session_synthesize, _taps and _pcm keep their behaviour on a session whose voices share one latch
+ * state and answer AFS_ERR_INVALID_ARGUMENT on a mixed one; afs_session_reset resets everything.  Both
+ * kinds of call may alternate on one session (they keep the latched frame in the same place).
+ * Not covered: afs_synthesizer.hpp, afs_multi_synthesize, target sequences, the one-lane solvers, a hop
+ * per voice, num_frames in device memory. */
+afs_status afs_session_restart_voices(afs_session *s, const int32_t *voices, const uint32_t *seeds, int32_t n);
+afs_status afs_session_synthesize_ragged(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                         const int32_t *num_frames, int32_t hop, double *out, int64_t out_stride,
+                                         double *taps_out, uint8_t *nonfinite, int32_t *produced,
+                                         afs_report *report);
+afs_status afs_session_latched(afs_session *s, uint8_t *flags);
+
 /* ---- Signal taps: section pressures and branch currents beside the audio -----------------
  * TdsModel::getSectionPressure / getSectionFlow (TdsModel.cpp:1715-1734) for whole batches: up to
  * AFS_MAX_TAPS quantities of the tube's state, one value per audio sample.  Value t of a tap is the
@@ -360,11 +405,17 @@ afs_status afs_synthesize_ragged_pcm(afs_ctx *ctx, const afs_frame *frames, int6
                                      int16_t *pcm, int64_t pcm_stride, uint8_t *nonfinite, afs_report *report);
 afs_status afs_session_synthesize_pcm(afs_session *s, const afs_frame *frames, int32_t num_samples, int16_t *pcm,
                                       uint8_t *nonfinite, int32_t *produced, afs_report *report);
+/* (the voice pool's call, see afs_session_synthesize_ragged) */
+afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                             const int32_t *num_frames, int32_t hop, int16_t *pcm,
+                                             int64_t pcm_stride, uint8_t *nonfinite, int32_t *produced,
+                                             afs_report *report);
 /* Diagnostics: the device memory the context holds now (its buffers grow on demand and are kept).
  * total_bytes: all of it; sample_buffer_bytes: the part that holds one fp64 value per
  * utterance-sample -- the flow and section-25 windows of a launch, a staged fp64 out or taps of a host
  * caller, a shard's fp64 audio (afs_multi_synthesize).  A context that has only run PCM calls holds
- * the two windows alone. */
+ * the two windows alone.  total_bytes counts the frame rows of a pool call
+ * (afs_session_synthesize_ragged: batch x (frame_stride + 1) frames, kept by the context). */
 typedef struct afs_memory_info {
   int64_t total_bytes;
   int64_t sample_buffer_bytes;
