@@ -46,6 +46,7 @@ EXPORTED = (
     "afs_synthesize_pcm", "afs_synthesize_ragged_pcm", "afs_session_synthesize_pcm", "afs_memory_info_get",
     "afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
     "afs_session_latched",
+    "afs_session_voice_state_bytes", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
 )
 
 
@@ -181,8 +182,13 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_session_synthesize_ragged_pcm.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, vp, ctypes.c_int64,
                                                       vp, vp, ctypes.POINTER(AfsReport)]
     lib.afs_session_latched.argtypes = [vp, vp]
+    lib.afs_session_voice_state_bytes.argtypes = [vp]
+    lib.afs_session_voice_state_bytes.restype = ctypes.c_int64
+    lib.afs_session_save_voices.argtypes = [vp, vp, ctypes.c_int32, vp]
+    lib.afs_session_load_voices.argtypes = [vp, vp, ctypes.c_int32, vp]
+    lib.afs_session_copy_voices.argtypes = [vp, vp, vp, vp, ctypes.c_int32]
     for name in ("afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
-                 "afs_session_latched"):
+                 "afs_session_latched", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices"):
         getattr(lib, name).restype = ctypes.c_int
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",

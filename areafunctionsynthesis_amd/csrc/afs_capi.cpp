@@ -1170,6 +1170,9 @@ afs_status afs_session_reset(afs_session *s, const uint32_t *seeds) {
                               seeds ? s->seeds.as<uint32_t>() : nullptr, s->lanes);
   if (st != AFS_OK) return st;
   s->latch.assign((size_t)s->B, 0);
+  s->seed_of.assign((size_t)s->B, 0);  // (device seeds: not known here)
+  if (!seeds || !is_device_ptr(seeds))
+    for (int u = 0; u < s->B; ++u) s->seed_of[(size_t)u] = seeds ? seeds[u] : (uint32_t)u + 1u;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }
@@ -1412,6 +1415,64 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   return fill_report(c, rep, done(samples));
 }
 
+// ---- voice records: a voice's state out of its slot, into another, or into many (afs_voice_state.h) ----
+
+// the header of a record of this session: what every record loaded into it must carry, and with the
+// voice's latch flag and seed what a saved one does
+static afs::VoiceStateHeader voice_header(const afs_session *s, bool latched, uint32_t seed) {
+  const afs::VoiceStateLayout L = afs::voice_state_layout_for(s->lanes);
+  const afs_config &cfg = s->ctx->cfg;
+  return afs::voice_state_header(s->lanes, L.bytes[0] / s->lanes, L.bytes[1] / (int64_t)sizeof(double),
+                                 cfg.sampling_rate_hz, cfg.options, latched, seed);
+}
+
+static afs::VoiceStateBuffers voice_buffers(const afs_session *s) {
+  return {s->tree_lanes.as<char>(), s->ws.as<char>(), s->pair.as<char>()};
+}
+
+// a host list of n voices of the session, each listed once when `distinct`
+static afs_status voice_list_check(afs_ctx *c, const char *fn, const char *what, const afs_session *s,
+                                   const int32_t *voices, int32_t n, bool distinct) {
+  if (is_device_ptr(voices)) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: %s is a host array", fn, what);
+  std::vector<uint8_t> listed((size_t)s->B, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t v = voices[i];
+    if (v < 0 || v >= s->B)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: %s[%d] = %d outside 0..%d", fn, what, i, v, s->B - 1);
+    if (distinct && listed[(size_t)v]) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: voice %d listed twice in %s", fn, v, what);
+    listed[(size_t)v] = 1;
+  }
+  return AFS_OK;
+}
+
+// The context's pinned buffer for a call's small host arrays (as pool_layout uses it): at least `bytes`,
+// free to rewrite once the last upload from it has been read.  The caller records ev_ragged behind its
+// own copies.
+static afs_status pinned_lists(afs_ctx *c, size_t bytes, char **h) {
+  if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
+  HIP_TRY(c, c->ragged_host.reserve(bytes));
+  *h = c->ragged_host.as<char>();
+  return AFS_OK;
+}
+
+// what save and load check before they touch anything (n == 0 passes: the caller then returns at once)
+static afs_status voice_state_args(afs_session *s, const char *fn, const int32_t *voices, int32_t n, const void *state,
+                                   bool *state_dev) {
+  afs_ctx *c = s->ctx;
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (n < 0 || (n > 0 && (!voices || !state)))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need n >= 0 voices and their records", fn);
+  if (n == 0) return AFS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const afs_status st = voice_list_check(c, fn, "voices", s, voices, n, true);
+  if (st != AFS_OK) return st;
+  *state_dev = is_device_ptr(state);
+  if (*state_dev && (reinterpret_cast<uintptr_t>(state) & 15))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: device records are 16-byte aligned", fn);
+  return AFS_OK;
+}
+
 extern "C" {
 
 afs_status afs_session_synthesize(afs_session *s, const afs_frame *frames, int32_t n, double *out,
@@ -1477,13 +1538,143 @@ afs_status afs_session_restart_voices(afs_session *s, const int32_t *voices, con
   HIP_TRY(c, afs::launch_voice_reset(s->tree_lanes.data(), s->ws.as<double>(), (const int32_t *)d,
                                      seeds ? (const uint32_t *)(d + lb) : nullptr, n, s->lanes, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int32_t i = 0; i < n; ++i) s->latch[(size_t)voices[i]] = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    s->latch[(size_t)voices[i]] = 0;
+    s->seed_of[(size_t)voices[i]] = seeds ? seeds[i] : (uint32_t)voices[i] + 1u;
+  }
   return AFS_OK;
 }
 
 afs_status afs_session_latched(afs_session *s, uint8_t *flags) {
   if (!s || !flags) return AFS_ERR_INVALID_ARGUMENT;
   for (int u = 0; u < s->B; ++u) flags[u] = s->latch[(size_t)u] ? 1 : 0;
+  return AFS_OK;
+}
+
+int64_t afs_session_voice_state_bytes(const afs_session *s) {
+  if (!s || !tree(s->ctx)) return 0;
+  return afs::voice_state_layout_for(s->lanes).record_bytes;
+}
+
+// The headers are written here, into the pinned buffer behind the voice list, and copied to the front
+// of each record; the gather fills in the payloads behind them.  A host `state` gets the records from
+// the context's staging buffer, whole.
+afs_status afs_session_save_voices(afs_session *s, const int32_t *voices, int32_t n, void *state) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  afs_ctx *c = s->ctx;
+  const char *fn = "afs_session_save_voices";
+  bool dev = false;
+  afs_status st = voice_state_args(s, fn, voices, n, state, &dev);
+  if (st != AFS_OK || n == 0) return st;
+  const size_t rb = (size_t)afs::voice_state_layout_for(s->lanes).record_bytes;
+  const size_t lb = (size_t)afs::voice_state_pad16((int64_t)n * 4), hb = (size_t)n * sizeof(afs::VoiceStateHeader);
+  char *h = nullptr;
+  if ((st = pinned_lists(c, lb + hb, &h)) != AFS_OK) return st;
+  std::memcpy(h, voices, (size_t)n * sizeof(int32_t));
+  for (int32_t i = 0; i < n; ++i) {
+    const size_t v = (size_t)voices[i];
+    const afs::VoiceStateHeader hdr = voice_header(s, s->latch[v] != 0, s->seed_of[v]);
+    std::memcpy(h + lb + (size_t)i * sizeof hdr, &hdr, sizeof hdr);
+  }
+  HIP_TRY(c, c->pool_list.reserve(lb));
+  char *records = static_cast<char *>(state);
+  if (!dev) {
+    HIP_TRY(c, c->voice_stage.reserve((size_t)n * rb));
+    records = c->voice_stage.as<char>();
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->pool_list.data(), h, lb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpy2DAsync(records, rb, h + lb, sizeof(afs::VoiceStateHeader), sizeof(afs::VoiceStateHeader),
+                              (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  HIP_TRY(c, afs::launch_voice_gather(voice_buffers(s), c->pool_list.as<int32_t>(), n, s->lanes, records, c->stream));
+  if (!dev) HIP_TRY(c, hipMemcpyAsync(state, records, (size_t)n * rb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return AFS_OK;
+}
+
+// Every header is read (a device state's through the pinned buffer, with a wait) and checked against
+// the session's own before anything is written; then the upload of host records and the scatter.
+afs_status afs_session_load_voices(afs_session *s, const int32_t *voices, int32_t n, const void *state) {
+  if (!s) return AFS_ERR_INVALID_ARGUMENT;
+  afs_ctx *c = s->ctx;
+  const char *fn = "afs_session_load_voices";
+  bool dev = false;
+  afs_status st = voice_state_args(s, fn, voices, n, state, &dev);
+  if (st != AFS_OK || n == 0) return st;
+  const size_t rb = (size_t)afs::voice_state_layout_for(s->lanes).record_bytes;
+  const size_t lb = (size_t)afs::voice_state_pad16((int64_t)n * 4), hb = (size_t)n * sizeof(afs::VoiceStateHeader);
+  char *h = nullptr;
+  if ((st = pinned_lists(c, lb + hb, &h)) != AFS_OK) return st;
+  std::vector<afs::VoiceStateHeader> hdr((size_t)n);
+  if (dev) {
+    HIP_TRY(c, hipMemcpy2DAsync(h + lb, sizeof(afs::VoiceStateHeader), state, rb, sizeof(afs::VoiceStateHeader),
+                                (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::memcpy(hdr.data(), h + lb, hb);
+  } else {
+    for (int32_t i = 0; i < n; ++i)
+      std::memcpy(&hdr[(size_t)i], static_cast<const char *>(state) + (size_t)i * rb, sizeof(afs::VoiceStateHeader));
+  }
+  const afs::VoiceStateHeader want = voice_header(s, false, 0);
+  for (int32_t i = 0; i < n; ++i)
+    if (const char *why = afs::voice_state_mismatch(hdr[(size_t)i], want))
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: record %d does not fit this session: %s", fn, i, why);
+  std::memcpy(h, voices, (size_t)n * sizeof(int32_t));
+  HIP_TRY(c, c->pool_list.reserve(lb));
+  const char *records = static_cast<const char *>(state);
+  if (!dev) {
+    HIP_TRY(c, c->voice_stage.reserve((size_t)n * rb));
+    HIP_TRY(c, hipMemcpyAsync(c->voice_stage.data(), state, (size_t)n * rb, hipMemcpyHostToDevice, c->stream));
+    records = c->voice_stage.as<char>();
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->pool_list.data(), h, lb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  HIP_TRY(c, afs::launch_voice_scatter(voice_buffers(s), c->pool_list.as<int32_t>(), n, s->lanes, records, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int32_t i = 0; i < n; ++i) {
+    s->latch[(size_t)voices[i]] = hdr[(size_t)i].latched ? 1 : 0;
+    s->seed_of[(size_t)voices[i]] = hdr[(size_t)i].seed;
+  }
+  return AFS_OK;
+}
+
+// A gather of the sources into the context's staging buffer, then a scatter into the destinations: on
+// one stream, so every source is read before any destination is written (a swap on one session).
+afs_status afs_session_copy_voices(afs_session *dst, const int32_t *dst_voices, afs_session *src,
+                                   const int32_t *src_voices, int32_t n) {
+  if (!dst || !src) return AFS_ERR_INVALID_ARGUMENT;
+  afs_ctx *c = dst->ctx;
+  const char *fn = "afs_session_copy_voices";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (src->ctx != c) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: the sessions belong to different contexts", fn);
+  if (src->lanes != dst->lanes)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: the sessions differ in lane width (%d, %d)", fn, src->lanes, dst->lanes);
+  if (n < 0 || (n > 0 && (!dst_voices || !src_voices)))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need n >= 0 voices in both lists", fn);
+  if (n == 0) return AFS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  afs_status st;
+  if ((st = voice_list_check(c, fn, "dst_voices", dst, dst_voices, n, true)) != AFS_OK) return st;
+  if ((st = voice_list_check(c, fn, "src_voices", src, src_voices, n, false)) != AFS_OK) return st;
+  const size_t rb = (size_t)afs::voice_state_layout_for(dst->lanes).record_bytes;
+  const size_t lb = (size_t)afs::voice_state_pad16((int64_t)n * 4);
+  char *h = nullptr;
+  if ((st = pinned_lists(c, 2 * lb, &h)) != AFS_OK) return st;
+  std::memcpy(h, src_voices, (size_t)n * sizeof(int32_t));
+  std::memcpy(h + lb, dst_voices, (size_t)n * sizeof(int32_t));
+  HIP_TRY(c, c->pool_list.reserve(2 * lb));
+  HIP_TRY(c, c->voice_stage.reserve((size_t)n * rb));
+  char *d = c->pool_list.as<char>();
+  HIP_TRY(c, hipMemcpyAsync(d, h, 2 * lb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  HIP_TRY(c, afs::launch_voice_gather(voice_buffers(src), (const int32_t *)d, n, src->lanes, c->voice_stage.data(), c->stream));
+  HIP_TRY(c, afs::launch_voice_scatter(voice_buffers(dst), (const int32_t *)(d + lb), n, dst->lanes,
+                                       c->voice_stage.data(), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<uint8_t> lat((size_t)n);
+  std::vector<uint32_t> seed((size_t)n);
+  for (int32_t i = 0; i < n; ++i) lat[(size_t)i] = src->latch[(size_t)src_voices[i]], seed[(size_t)i] = src->seed_of[(size_t)src_voices[i]];
+  for (int32_t i = 0; i < n; ++i) dst->latch[(size_t)dst_voices[i]] = lat[(size_t)i], dst->seed_of[(size_t)dst_voices[i]] = seed[(size_t)i];
   return AFS_OK;
 }
 

@@ -63,6 +63,9 @@ struct afs_ctx {
   // the call's own, nothing in it outlives the call -- the latched frames stay in the session's pair), and
   // the voice and seed lists of afs_session_restart_voices
   afs::DeviceBuf pool_rows, pool_list;
+  // voice records in flight (afs_voice_state.h): a host caller's records of afs_session_save_voices /
+  // _load_voices, and what afs_session_copy_voices gathers before it scatters
+  afs::DeviceBuf voice_stage;
   int32_t last_B = 0;        // batch of the last whole-trajectory call (afs_rng_draws)
   afs::DeviceBuf dcount;  // int32_t: the non-finite utterances of a call
   afs::PinnedBuf hcount;  // pinned host copy of dcount
@@ -79,7 +82,7 @@ struct afs_ctx {
   std::vector<const afs::DeviceBuf *> device_bufs() const {
     return {&dev_tab, &ws, &rng, &tree_lanes, &stage_in, &stage_out, &stage_seeds, &tgt, &plan, &hops, &p25,
             &plan_work, &flow, &stage_pcm, &keys, &sort_tmp, &order_buf, &stage_nf, &m_out, &m_pcm, &m_nf, &m_root,
-            &stage_taps, &ragged, &dcount, &pool_rows, &pool_list};
+            &stage_taps, &ragged, &dcount, &pool_rows, &pool_list, &voice_stage};
   }
   std::vector<const afs::DeviceBuf *> sample_bufs() const { return {&flow, &p25, &stage_out, &stage_taps, &m_out}; }
 };
@@ -97,6 +100,9 @@ struct afs_session {
   // per voice: whether pair[u][0] holds its latched frame (the first frame after create / reset /
   // afs_session_restart_voices only latches).  The lock-step calls need one state for all voices.
   std::vector<uint8_t> latch;
+  // per voice: the seed it was last given (create / reset / restart, or with a loaded or copied state);
+  // 0: not known (seeds given in device memory).  Goes into a saved record's header, nothing reads it.
+  std::vector<uint32_t> seed_of;
   bool all_latched(bool v) const {
     for (uint8_t x : latch)
       if ((x != 0) != v) return false;

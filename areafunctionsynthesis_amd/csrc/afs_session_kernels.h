@@ -1,6 +1,7 @@
 // afs_session_kernels.h -- the per-voice lifecycle of a session's voice pool (session_kernels.hip;
-// afs_session_restart_voices, afs_session_synthesize_ragged): the reset of listed voices and the frame
-// rows of a pool call.  The synthesis kernels themselves (tds_tree.hip, tds_plan.hip) know nothing of it.
+// afs_session_restart_voices, afs_session_synthesize_ragged, afs_session_save_voices and its kin): the
+// reset of listed voices, the frame rows of a pool call, and voice records in and out of a session.  The
+// synthesis kernels themselves (tds_tree.hip, tds_plan.hip) know nothing of it.
 #pragma once
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "afs_model.h"
+#include "afs_voice_state.h"
 
 namespace afs {
 
@@ -26,6 +28,23 @@ hipError_t launch_voice_reset(void *lane_state, double *lds_state, const int32_t
 // frames, rows and pair are 16-byte aligned.
 hipError_t launch_pool_rows(const afs_frame *frames, int64_t frame_stride, const int32_t *count,
                             const int32_t *latched, int B, afs_frame *rows, afs_frame *pair, hipStream_t st);
+
+// Voice records (afs_voice_state.h; afs_session_save_voices, _load_voices, _copy_voices).  The session's
+// three buffers that hold a voice: the lane registers, the saved LDS images, the frame pairs.
+struct VoiceStateBuffers {
+  char *lanes, *lds, *pair;
+};
+// the record layout of a session of `lanes` lanes per utterance (Lane<lanes>, X_TOTAL, afs_frame)
+VoiceStateLayout voice_state_layout_for(int lanes);
+// Gather: the payload of record i of records[n] (device, 16-byte aligned) becomes a copy of the state of
+// voice voices[i] (a device list; a voice may repeat), bit for bit; the records' headers and the session
+// are not touched.  Scatter: voice voices[i] (distinct) gets the payload of record i; no byte of another
+// voice, and none of pair[u][1], is written.  One 16-byte vector per thread, a record over 7 (16
+// lanes) or 11 (64 lanes) blocks of four waves.
+hipError_t launch_voice_gather(const VoiceStateBuffers &s, const int32_t *voices, int n, int lanes, void *records,
+                               hipStream_t st);
+hipError_t launch_voice_scatter(const VoiceStateBuffers &s, const int32_t *voices, int n, int lanes, const void *records,
+                                hipStream_t st);
 
 // load the code object on the current device (afs_create; see afs_tree.h)
 hipError_t preload_session_kernels();

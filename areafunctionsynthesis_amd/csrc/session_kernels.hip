@@ -1,12 +1,14 @@
 // session_kernels.hip -- the per-voice lifecycle of a session's voice pool (afs_session_kernels.h):
-// the reset of listed voices and the frame rows of a pool call.  A translation unit of its own: the
-// synthesis kernels' code object (tds_tree.hip) stays what it was, register counts included.
+// the reset of listed voices, the frame rows of a pool call, and the gather and scatter of voice
+// records (afs_voice_state.h).  A translation unit of its own: the synthesis kernels' code object
+// (tds_tree.hip) stays what it was, register counts included.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "afs_session_kernels.h"
 #include "afs_tree.h"
+#include "afs_voice_state.h"
 #include "tree_core.h"
 
 namespace afs {
@@ -68,6 +70,45 @@ __global__ void __launch_bounds__(64 * ROWS_WAVES) pool_rows_kernel(const uint4 
   if (two) dst[lane + 64] = a1;
 }
 
+// ---- voice records: session buffers <-> packed records (afs_voice_state.h) ----
+
+static_assert((sizeof(Lane<TREE_W>) * TREE_W) % 16 == 0 && (sizeof(Lane<64>) * 64) % 16 == 0 &&
+                  (X_TOTAL * sizeof(double)) % 16 == 0 && sizeof(afs_frame) % 16 == 0,
+              "every part of a voice record is whole 16-byte vectors");
+constexpr int STATE_WAVES = 4;  // waves per block: 256 consecutive vectors (4 KiB) of one record
+
+// Block (i, k) moves payload vectors 256 k .. 256 k + 255 of record i, the voice voices[i]: a thread one
+// 16-byte vector, consecutive lanes consecutive vectors, a record (1607 vectors at 16 lanes, 2791 at 64)
+// spread over 7 or 11 blocks.  The three parts sit in three buffers of the session; a wave that spans
+// the border of two parts touches both.  False: the thread has no vector (past the record's end).
+__device__ inline bool voice_state_thread(const VoiceStateBuffers &s, const int32_t *voices, int n,
+                                          const VoiceStateLayout &L, char *records, uint4 **in_session,
+                                          uint4 **in_record) {
+  const int i = blockIdx.x;
+  const int64_t v = (int64_t)blockIdx.y * (64 * STATE_WAVES) + threadIdx.x;
+  if (i >= n || v >= voice_state_payload_vecs(L)) return false;
+  const VoiceStateVec at = voice_state_vec(L, v, voices[i]);
+  if (at.part < 0) return false;
+  char *base = at.part == 0 ? s.lanes : at.part == 1 ? s.lds : s.pair;
+  *in_session = reinterpret_cast<uint4 *>(base + at.session_off);
+  *in_record = reinterpret_cast<uint4 *>(records + (int64_t)i * L.record_bytes + at.record_off);
+  return true;
+}
+
+// session -> records: reads the session's buffers only (a voice may be listed more than once)
+__global__ void __launch_bounds__(64 * STATE_WAVES) voice_gather_kernel(VoiceStateBuffers s, const int32_t *voices,
+                                                                       int n, VoiceStateLayout L, char *records) {
+  uint4 *in_session, *in_record;
+  if (voice_state_thread(s, voices, n, L, records, &in_session, &in_record)) *in_record = *in_session;
+}
+
+// records -> session: writes the listed voices' parts and nothing else (the voices are distinct)
+__global__ void __launch_bounds__(64 * STATE_WAVES) voice_scatter_kernel(VoiceStateBuffers s, const int32_t *voices,
+                                                                        int n, VoiceStateLayout L, char *records) {
+  uint4 *in_session, *in_record;
+  if (voice_state_thread(s, voices, n, L, records, &in_session, &in_record)) *in_session = *in_record;
+}
+
 }  // namespace
 
 hipError_t launch_voice_reset(void *lane_state, double *lds_state, const int32_t *voices, const uint32_t *seeds, int n,
@@ -94,12 +135,45 @@ hipError_t launch_pool_rows(const afs_frame *frames, int64_t frame_stride, const
   return hipGetLastError();
 }
 
+VoiceStateLayout voice_state_layout_for(int lanes) {
+  return voice_state_layout(lanes, lanes == 64 ? (int64_t)sizeof(Lane<64>) : (int64_t)sizeof(Lane<TREE_W>), X_TOTAL,
+                            (int64_t)sizeof(afs_frame));
+}
+
+static hipError_t launch_voice_state(bool gather, const VoiceStateBuffers &s, const int32_t *voices, int n, int lanes,
+                                     void *records, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if ((reinterpret_cast<uintptr_t>(s.lanes) | reinterpret_cast<uintptr_t>(s.lds) | reinterpret_cast<uintptr_t>(s.pair) |
+       reinterpret_cast<uintptr_t>(records)) & 15)
+    return hipErrorInvalidValue;
+  const VoiceStateLayout L = voice_state_layout_for(lanes);
+  const int64_t vecs = voice_state_payload_vecs(L);
+  const dim3 grid((unsigned)n, (unsigned)((vecs + 64 * STATE_WAVES - 1) / (64 * STATE_WAVES))), block(64 * STATE_WAVES);
+  if (gather)
+    hipLaunchKernelGGL(voice_gather_kernel, grid, block, 0, st, s, voices, n, L, (char *)records);
+  else
+    hipLaunchKernelGGL(voice_scatter_kernel, grid, block, 0, st, s, voices, n, L, (char *)records);
+  return hipGetLastError();
+}
+
+hipError_t launch_voice_gather(const VoiceStateBuffers &s, const int32_t *voices, int n, int lanes, void *records,
+                               hipStream_t st) {
+  return launch_voice_state(true, s, voices, n, lanes, records, st);
+}
+
+hipError_t launch_voice_scatter(const VoiceStateBuffers &s, const int32_t *voices, int n, int lanes, const void *records,
+                                hipStream_t st) {
+  return launch_voice_state(false, s, voices, n, lanes, const_cast<void *>(records), st);
+}
+
 hipError_t preload_session_kernels() {
   hipError_t e = hipSuccess;
   hipFuncAttributes at;
   for (const void *k : {reinterpret_cast<const void *>(voice_reset_kernel<TREE_W>),
                         reinterpret_cast<const void *>(voice_reset_kernel<64>),
-                        reinterpret_cast<const void *>(pool_rows_kernel)}) {
+                        reinterpret_cast<const void *>(pool_rows_kernel),
+                        reinterpret_cast<const void *>(voice_gather_kernel),
+                        reinterpret_cast<const void *>(voice_scatter_kernel)}) {
     const hipError_t x = hipFuncGetAttributes(&at, k);
     if (e == hipSuccess) e = x;
   }

@@ -9,6 +9,9 @@
 * :meth:`Context.synthesize_stream` -- continuous batching: a corpus streamed through a pool of
   voices (:meth:`Synthesizer.synthesize_frames`, :meth:`Synthesizer.restart`), a few frames per
   voice and call.
+* :meth:`Context.synthesize_candidates` -- branching: a prefix played once, forked into K voices
+  (:meth:`Synthesizer.fork`, :meth:`Synthesizer.save_voices`, :meth:`Synthesizer.load_voices`,
+  :meth:`Synthesizer.copy_voices`), each playing its own continuation.
 * :meth:`Context.play_target_sequences` -- ``Synthesizer::playTargetSequence``
   (``src/Backend/Synthesizer.cpp:1299-1422``) for ``B`` utterances: four target shapes each,
   per-sample area-function tubes built on the GPU.
@@ -316,6 +319,24 @@ class Context:
         try:
             yield from stream_utterances(session, utterances, hop, chunk_frames, seeds=seeds, pcm=pcm,
                                          finished=finished)
+        finally:
+            session.close()
+
+    def synthesize_candidates(self, prefix, candidates, hop: int, seed: int = 1, pcm: bool = False):
+        """Branching (tree solver): ``prefix[Fp]`` is played once, on voice 0 of a session of K voices
+        seeded ``seed``; that voice is forked into all K, and voice k plays ``candidates[k][Fc]``
+        (a ``[K, Fc]`` FRAME_DTYPE array).  Returns the candidates' audio ``[K, Fc*hop]`` -- float64, or
+        int16 with ``pcm`` -- row k bit for bit the last ``Fc*hop`` samples of
+        ``synthesize(concat(prefix, candidates[k])[None], hop, seeds=[seed])`` on a context of the
+        session's lane width: prefix + K x candidate samples are computed instead of K x (prefix +
+        candidate)."""
+        candidates = np.ascontiguousarray(candidates, dtype=FRAME_DTYPE)
+        if candidates.ndim != 2 or candidates.shape[0] < 1:
+            raise ValueError("candidates must be a FRAME_DTYPE array [K, Fc]")
+        K = candidates.shape[0]
+        session = Synthesizer(self, K, np.full(K, int(seed), dtype=np.uint32))
+        try:
+            return branch_candidates(session, prefix, candidates, hop, pcm=pcm)
         finally:
             session.close()
 
@@ -791,6 +812,58 @@ class Synthesizer:
                      "nonfinite": nonfinite},)
         return res
 
+    @property
+    def voice_state_bytes(self) -> int:
+        """afs_session_voice_state_bytes: the size of one voice's record (tree solver)."""
+        n = int(self._lib.afs_session_voice_state_bytes(self._h))
+        if n <= 0:
+            raise _native.AfsError("afs_session_voice_state_bytes: " + _native.STATUS[5] + " (tree solver only)")
+        return n
+
+    def save_voices(self, voices, out=None):
+        """afs_session_save_voices: the records of the listed voices (distinct indices), ``uint8[n,
+        voice_state_bytes]`` -- a numpy array, or ``out``, which may be a uint8 GPU tensor of that shape
+        (16-byte aligned).  The session does not change."""
+        v = np.ascontiguousarray(voices, dtype=np.int32).reshape(-1)
+        size = self.voice_state_bytes
+        if out is None:
+            out = np.zeros((v.size, size), dtype=np.uint8)
+        if _nbytes(out) != v.size * size:
+            raise ValueError("out must hold n records of voice_state_bytes")
+        _native.check(self._lib.afs_session_save_voices(self._h, _vp(_addr(v)), int(v.size), _vp(_addr(out))),
+                      self.ctx.handle, "afs_session_save_voices")
+        return out
+
+    def load_voices(self, voices, state) -> None:
+        """afs_session_load_voices: voice ``voices[i]`` (distinct) continues as the voice saved in record
+        ``state[i]`` would have -- whichever slot, session or context of the same sampling rate, options
+        and lane width it was saved from.  ``state``: uint8 ``[n, voice_state_bytes]``, numpy or GPU
+        tensor.  No other voice changes."""
+        v = np.ascontiguousarray(voices, dtype=np.int32).reshape(-1)
+        if isinstance(state, np.ndarray):
+            state = np.ascontiguousarray(state, dtype=np.uint8)
+        if _nbytes(state) != v.size * self.voice_state_bytes:
+            raise ValueError("state must hold n records of voice_state_bytes")
+        _native.check(self._lib.afs_session_load_voices(self._h, _vp(_addr(v)), int(v.size), _vp(_addr(state))),
+                      self.ctx.handle, "afs_session_load_voices")
+
+    def copy_voices(self, dst_voices, src_voices, src: Optional["Synthesizer"] = None) -> None:
+        """afs_session_copy_voices: voice ``src_voices[i]`` of ``src`` (None: this session) becomes voice
+        ``dst_voices[i]`` of this one.  ``dst_voices`` are distinct, ``src_voices`` may repeat; on one
+        session the lists may overlap (every source is read first: ``copy_voices([0, 1], [1, 0])`` swaps)."""
+        d = np.ascontiguousarray(dst_voices, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(src_voices, dtype=np.int32).reshape(-1)
+        if d.shape != s.shape:
+            raise ValueError("one source per destination")
+        src = self if src is None else src
+        _native.check(self._lib.afs_session_copy_voices(self._h, _vp(_addr(d)), src._h, _vp(_addr(s)), int(d.size)),
+                      self.ctx.handle, "afs_session_copy_voices")
+
+    def fork(self, voice: int, into) -> None:
+        """One voice copied into the voices ``into`` (distinct): each continues from the same instant."""
+        into = np.ascontiguousarray(into, dtype=np.int32).reshape(-1)
+        self.copy_voices(into, np.full(into.shape, int(voice), dtype=np.int32))
+
     def rng_draws(self) -> np.ndarray:
         """rand() calls of every voice since construction / the last reset (tree solver)."""
         d = np.zeros(self.batch, dtype=np.int64)
@@ -876,3 +949,30 @@ def stream_utterances(session, utterances, hop: int, chunk_frames: int, seeds=No
                 done = (index[u], audio[u])
                 index[u], frames[u], audio[u] = -1, None, None
                 yield done
+
+
+def branch_candidates(session, prefix, candidates, hop: int, pcm: bool = False):
+    """The branching behind :meth:`Context.synthesize_candidates`, written against what it needs of a
+    session of K voices: ``batch``, ``synthesize_frames(frames, num_frames, hop, pcm=)`` and ``fork(voice,
+    into)``.  Three calls: the prefix on voice 0 beside K - 1 idle voices, one fork of voice 0 into the
+    others, then every voice its candidate.  Returns the second call's audio ``[K, Fc*hop]``."""
+    prefix = np.ascontiguousarray(prefix, dtype=FRAME_DTYPE).reshape(-1)
+    candidates = np.ascontiguousarray(candidates, dtype=FRAME_DTYPE)
+    K, hop = int(session.batch), int(hop)
+    if candidates.ndim != 2 or candidates.shape[0] != K or candidates.shape[1] < 1:
+        raise ValueError("candidates must hold one row of at least one frame per voice")
+    if len(prefix) < 1 or hop < 1:
+        raise ValueError("the prefix needs at least one frame (the one the candidates start from) and hop >= 1")
+    Fp, Fc = len(prefix), candidates.shape[1]
+    rows = np.zeros((K, Fp), dtype=FRAME_DTYPE)
+    rows[0] = prefix
+    counts = np.zeros(K, dtype=np.int32)
+    counts[0] = Fp
+    session.synthesize_frames(rows, counts, hop, pcm=pcm)
+    if K > 1:
+        session.fork(0, np.arange(1, K, dtype=np.int32))
+    res = session.synthesize_frames(candidates, np.full(K, Fc, dtype=np.int32), hop, pcm=pcm)
+    audio, produced = res[0], res[1]
+    if not (np.asarray(produced) == Fc * hop).all():
+        raise RuntimeError("a candidate produced other than Fc*hop samples")
+    return audio[:, :Fc * hop]

@@ -335,6 +335,42 @@ afs_status afs_session_synthesize_ragged(afs_session *s, const afs_frame *frames
                                          afs_report *report);
 afs_status afs_session_latched(afs_session *s, uint8_t *flags);
 
+/* ---- Voice snapshots: save, load and fork the voices of a session ---------------------------
+ * A voice's state leaves its slot as a record of afs_session_voice_state_bytes bytes (a multiple of 16;
+ * 0 for a session of a one-lane solver): a fixed header, then the voice's device state verbatim -- its
+ * lane registers, its saved LDS image (output and tone filter state, non-finite flag, rand() ring and
+ * draw count, sample position) and its latched frame, each part padded to 16 bytes.
+ * The header carries a magic and layout version, the lane width, the sizes of the two state parts, the
+ * sampling rate, the afs_options, the voice's latched flag and, for information, the seed it was given
+ * (0: not known).  Tree solver only (else AFS_ERR_UNSUPPORTED).  voices, dst_voices and src_voices are
+ * HOST arrays; state holds n records and is host memory, or device memory aligned to 16 bytes.  Like
+ * every session call these wait for their work.
+ *
+ * afs_session_save_voices: record i receives voice voices[i] (distinct); no byte of the session changes.
+ * afs_session_load_voices: voice voices[i] (distinct) gets the state of record i -- lane state, LDS
+ * image, latched frame and latched flag; no byte of any other voice changes.  The slot, the session, its
+ * batch size and the context may be others than the ones saved from, provided the context has the same
+ * sampling rate, options and lane width: every header is checked before anything is written.
+ * afs_session_copy_voices: voice src_voices[i] of src becomes voice dst_voices[i] of dst.  dst_voices
+ * are distinct, src_voices may repeat (one voice into many: a fork), src == dst is allowed with
+ * overlapping lists (a swap): every source is read before any destination is written.  Both sessions
+ * belong to one context and have one lane width.
+ * After a load or a copy the voice continues, bit for bit, as the saved or source voice would have:
+ * rows, tap rows, afs_session_rng_draws, the non-finite flag and afs_session_latched, under every later
+ * call.  A voice saved unlatched loads unlatched; the lock-step calls keep their rule on mixed latch
+ * state.
+ * AFS_ERR_INVALID_ARGUMENT: a NULL pointer with n > 0, n < 0, a voice out of range, a destination or a
+ * saved voice listed twice, a misaligned device state, a record whose header does not fit the session
+ * (magic, version, lane width, state sizes, rate, options), sessions of different contexts or lane
+ * widths in a copy.  n == 0 is AFS_OK and does nothing.
+ * Not covered: conversion between the 16- and 64-lane layouts, the one-lane solvers,
+ * afs_synthesizer.hpp, records across library versions beyond the header check. */
+int64_t afs_session_voice_state_bytes(const afs_session *s);
+afs_status afs_session_save_voices(afs_session *s, const int32_t *voices, int32_t n, void *state);
+afs_status afs_session_load_voices(afs_session *s, const int32_t *voices, int32_t n, const void *state);
+afs_status afs_session_copy_voices(afs_session *dst, const int32_t *dst_voices, afs_session *src,
+                                   const int32_t *src_voices, int32_t n);
+
 /* ---- Signal taps: section pressures and branch currents beside the audio -----------------
  * TdsModel::getSectionPressure / getSectionFlow (TdsModel.cpp:1715-1734) for whole batches: up to
  * AFS_MAX_TAPS quantities of the tube's state, one value per audio sample.  Value t of a tap is the
@@ -415,7 +451,9 @@ afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *fr
  * utterance-sample -- the flow and section-25 windows of a launch, a staged fp64 out or taps of a host
  * caller, a shard's fp64 audio (afs_multi_synthesize).  A context that has only run PCM calls holds
  * the two windows alone.  total_bytes counts the frame rows of a pool call
- * (afs_session_synthesize_ragged: batch x (frame_stride + 1) frames, kept by the context). */
+ * (afs_session_synthesize_ragged: batch x (frame_stride + 1) frames, kept by the context) and the
+ * staging of voice records (afs_session_copy_voices, host records of _save_voices / _load_voices: n
+ * records, grown on demand and kept); neither is a sample buffer. */
 typedef struct afs_memory_info {
   int64_t total_bytes;
   int64_t sample_buffer_bytes;
