@@ -30,6 +30,8 @@ AFS_COMM_ID_BYTES = 128
 AFS_MAX_TAPS = 8  # afs.h
 AFS_TAP_PRESSURE = 0
 AFS_TAP_CURRENT = 1
+AFS_SAMPLE_I16 = 0  # afs.h afs_sample_format
+AFS_SAMPLE_F32 = 1
 
 # Every symbol include/afs.h declares.
 EXPORTED = (
@@ -47,6 +49,7 @@ EXPORTED = (
     "afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
     "afs_session_latched",
     "afs_session_voice_state_bytes", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
+    "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets", "afs_session_synthesize_ragged_packed",
 )
 
 
@@ -187,8 +190,17 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_session_save_voices.argtypes = [vp, vp, ctypes.c_int32, vp]
     lib.afs_session_load_voices.argtypes = [vp, vp, ctypes.c_int32, vp]
     lib.afs_session_copy_voices.argtypes = [vp, vp, vp, vp, ctypes.c_int32]
+    lib.afs_synthesize_f32.argtypes = [vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
+                                       vp, ctypes.POINTER(AfsReport)]
+    lib.afs_synthesize_ragged_packed.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, vp, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_ragged_offsets.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
+    lib.afs_session_synthesize_ragged_packed.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp,
+                                                         vp, vp, vp, ctypes.POINTER(AfsReport)]
     for name in ("afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
-                 "afs_session_latched", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices"):
+                 "afs_session_latched", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
+                 "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets",
+                 "afs_session_synthesize_ragged_packed"):
         getattr(lib, name).restype = ctypes.c_int
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",

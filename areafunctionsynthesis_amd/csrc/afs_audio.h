@@ -1,5 +1,6 @@
 // afs_audio.h -- output format stage: the int16 conversion (host and device: audio_kernels.hip's K3,
-// tree_core.h's PCM form of K6, tests/cpp/pcm_pack_main.cpp) and K3's launch (audio_kernels.hip).
+// tree_core.h's PCM form of K6, tests/cpp/pcm_pack_main.cpp), the float32 conversion (tree_core.h's
+// float32 form of K6, tests/cpp/f32_pack_main.cpp) and K3's launch (audio_kernels.hip).
 #pragma once
 
 #include <cstdint>
@@ -17,6 +18,10 @@ AFS_HD inline int16_t sample_to_int16(double x) {
   if (!(x == x)) return 0;
   return (int16_t)(int)(x * 32767.0);  // |x| <= 1: fits; truncation towards zero
 }
+
+// The float32 sample of the _f32 and packed calls: (float)x, round to nearest even; a NaN stays a NaN
+// and an infinity an infinity (the int16 form above has no way to carry them, this one has).
+AFS_HD inline float sample_to_f32(double x) { return (float)x; }
 
 }  // namespace afs
 

@@ -71,6 +71,9 @@ namespace {
 
 int64_t pad64(int64_t b) { return (b + 63) / 64 * 64; }
 
+// bytes of one sample of an afs_sample_format
+size_t sample_bytes(int format) { return format == AFS_SAMPLE_F32 ? sizeof(float) : sizeof(int16_t); }
+
 bool solver_ok(int32_t s) { return s == AFS_SOLVER_CHOLESKY || s == AFS_SOLVER_TREE || s == AFS_SOLVER_SOR; }
 
 // the cooperative kernel (noise-source plans from K5)
@@ -139,8 +142,13 @@ struct SynthCall {
   int64_t ostride = 0;
   // the _pcm calls (out is null): the audio as int16 to pcm[u * pstride + s]; the flows of each launch
   // pass through the context's flow window instead of `out`
-  int16_t *pcm = nullptr;
+  // (the _f32 and packed calls as well: `format` says what pcm points at, AFS_SAMPLE_I16 or
+  // AFS_SAMPLE_F32, and with row_base -- a device array of B row starts in samples, ragged calls only --
+  // utterance u's row starts at pcm[row_base[u]] instead of pcm[u * pstride])
+  void *pcm = nullptr;
   int64_t pstride = 0;
+  int format = AFS_SAMPLE_I16;
+  const int64_t *row_base = nullptr;
   void *ws = nullptr;
   int32_t *rng = nullptr;
   void *lanes = nullptr;
@@ -228,7 +236,8 @@ afs::PlanArgs plan_args(const afs_ctx *c, const afs_frame *frames, int64_t fstri
 }
 
 // K1 over samples [s0, s1) of the call, then K6 over them (both timed).  A _pcm call: K1's flows into
-// the flow window (rows of p25_stride, as p25's), K6's PCM form from there to the caller's pcm.
+// the flow window (rows of p25_stride, as p25's), K6's PCM form from there to the caller's pcm -- or its
+// float32 or packed form, by the call's format and row_base (afs_tree.h launch_tree_output_samples).
 afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, int64_t s1, const LaunchPlans &lp,
                                int64_t p25_stride) {
   const SlotOrder &so = call.so;
@@ -262,9 +271,10 @@ afs_status launch_synth_output(afs_ctx *c, const SynthCall &call, int64_t s0, in
   prof_pair(c, e1, e2, 0);
   // K6: the glottal-tone filter and the output stage of the launch's samples
   if (call.pcm)
-    HIP_TRY(c, afs::launch_tree_output_pcm(c->tab(), (double *)call.ws, out, p25_stride, s1 - s0, call.B, p25,
-                                           c->cfg.options.radiation_from_skin, call.pcm + s0, call.pstride, c->stream,
-                                           lp.skip, lp.skip_cap, call.ragged.row_hops, call.hop, s0));
+    HIP_TRY(c, afs::launch_tree_output_samples(c->tab(), (double *)call.ws, out, p25_stride, s1 - s0, call.B, p25,
+                                               c->cfg.options.radiation_from_skin, call.format, call.pcm, call.pstride,
+                                               call.row_base, c->stream, lp.skip, lp.skip_cap, call.ragged.row_hops,
+                                               call.hop, s0));
   else
     HIP_TRY(c, afs::launch_tree_output(c->tab(), (double *)call.ws, out, call.ostride, s1 - s0, call.B, p25, p25_stride,
                                        c->cfg.options.radiation_from_skin, c->stream, lp.skip, lp.skip_cap,
@@ -733,11 +743,14 @@ static afs_status taps_check(afs_ctx *c, const char *fn, const double *taps_out)
 // The launch layout of a ragged call and its per-row hop counts on the device: built on the host from
 // num_frames (afs_ragged_order.h), packed into the context's pinned buffer and uploaded on the stream
 // -- no host wait, except for the previous ragged call's upload when that has not been read yet.
-static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, int upb, int hop, SynthCall *call) {
+static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, int upb, int hop, SynthCall *call,
+                                const int64_t *row_base = nullptr) {
   const afs::RaggedOrder ro = afs::ragged_order(num_frames, B, upb, hop);
   const size_t slots = ro.order.size();
   const size_t end_bytes = (size_t)ro.grid * sizeof(int64_t), slot_bytes = slots * sizeof(int32_t);
-  const size_t bytes = end_bytes + 2 * slot_bytes + (size_t)B * sizeof(int32_t);
+  // (a packed call's row starts ride behind the hop counts, on an 8-byte boundary)
+  const size_t base0 = (end_bytes + 2 * slot_bytes + (size_t)B * sizeof(int32_t) + 7) / 8 * 8;
+  const size_t bytes = base0 + (row_base ? (size_t)B * sizeof(int64_t) : 0);
   if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
   else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
   HIP_TRY(c, c->ragged_host.reserve(bytes));
@@ -748,8 +761,10 @@ static afs_status ragged_layout(afs_ctx *c, const int32_t *num_frames, int B, in
   std::memcpy(h + end_bytes + slot_bytes, ro.standin.data(), slot_bytes);
   int32_t *hops = (int32_t *)(h + end_bytes + 2 * slot_bytes);
   for (int u = 0; u < B; ++u) hops[u] = num_frames[u] - 1;
+  if (row_base) std::memcpy(h + base0, row_base, (size_t)B * sizeof(int64_t));
   HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  call->row_base = row_base ? (const int64_t *)(d + base0) : nullptr;
   call->ragged.block_end = (const int64_t *)d;
   call->so.order = (const int32_t *)(d + end_bytes);
   call->so.grid = ro.grid;
@@ -771,8 +786,13 @@ struct Trajectories {
   double *out = nullptr;  // out[u * ostride + s]
   int64_t ostride = 0;
   double *taps_out = nullptr;  // the context's taps beside the audio, rows of ostride as well (null: none)
-  int16_t *pcm = nullptr;      // the _pcm calls, instead of out: pcm[u * pstride + s]
+  void *pcm = nullptr;         // the _pcm calls, instead of out: pcm[u * pstride + s]
   int64_t pstride = 0;
+  int format = AFS_SAMPLE_I16;  // ... its samples (the _f32 and packed calls: int16_t or float)
+  // the packed calls: row u at pcm[row_base[u] + s] instead (a host array the entry point has validated
+  // or built), and the samples the buffer spans, max(row_base[u] + T_u)
+  const int64_t *row_base = nullptr;
+  int64_t span = 0;
   int64_t samples = 0;         // what the report counts
   bool force_async = false;    // leave the stream running unless a host buffer needs a wait
   int lanes = 0;               // the tree kernel's lanes per utterance (0: chosen for B)
@@ -792,7 +812,7 @@ static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfini
   Frames fr;
   Seeds seeds;
   Staged<double> out, taps;
-  Staged<int16_t> pcm;
+  Staged<char> pcm;
   if ((s = frames_to_device(c, t.frames, (size_t)B * (size_t)t.fstride, &fr)) != AFS_OK) return s;
   if ((s = seeds_to_device(c, t.seeds, B, &seeds)) != AFS_OK) return s;
   // (a ragged call's host out and taps go up first and come back whole: what lies past each row's
@@ -800,8 +820,10 @@ static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfini
   if ((s = out.stage(c, t.out, out_bytes, c->stage_out, ragged)) != AFS_OK) return s;
   // (a host pcm likewise when its rows have padding; it reaches to the end of the last row's samples)
   const int64_t Tmax = (int64_t)(t.F - 1) * t.hop;
-  const size_t pcm_bytes = ((size_t)(B - 1) * (size_t)t.pstride + (size_t)Tmax) * sizeof(int16_t);
-  if ((s = pcm.stage(c, t.pcm, pcm_bytes, c->stage_pcm, ragged || t.pstride != Tmax)) != AFS_OK) return s;
+  // (a packed host out as well: its gaps are the caller's)
+  const size_t pcm_samples = t.row_base ? (size_t)t.span : (size_t)(B - 1) * (size_t)t.pstride + (size_t)Tmax;
+  const size_t pcm_bytes = pcm_samples * sample_bytes(t.format);
+  if ((s = pcm.stage(c, (char *)t.pcm, pcm_bytes, c->stage_pcm, ragged || t.pstride != Tmax)) != AFS_OK) return s;
   const int width = t.lanes > 0 ? t.lanes : lanes_for(c, B);
   if ((s = fresh_state(c, B, width, seeds.dev)) != AFS_OK) return s;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
@@ -810,9 +832,9 @@ static afs_status synth_core(afs_ctx *c, const Trajectories &t, uint8_t *nonfini
   call.frames = fr.dev, call.fstride = t.fstride, call.rows = B;
   call.ntrans = t.F - 1, call.hop = t.hop;
   call.out = out.dev, call.ostride = t.ostride;
-  call.pcm = pcm.dev, call.pstride = t.pstride;
+  call.pcm = pcm.dev, call.pstride = t.pstride, call.format = t.format;
   call.taps.out = taps.dev, call.taps.stride = t.ostride;
-  s = ragged ? ragged_layout(c, t.num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, t.hop, &call)
+  s = ragged ? ragged_layout(c, t.num_frames, B, width == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB, t.hop, &call, t.row_base)
              : shape_order(c, fr.dev, t.fstride, B, width, &call.so);
   if (s != AFS_OK) return s;
   if ((s = run_call(c, call)) != AFS_OK) return s;
@@ -955,6 +977,110 @@ afs_status afs_synthesize_ragged_pcm(afs_ctx *c, const afs_frame *frames, int64_
   t.frames = frames, t.fstride = fstride, t.num_frames = num_frames;
   t.seeds = seeds, t.B = B, t.hop = hop;
   t.pcm = pcm, t.pstride = pstride;
+  return synth_core(c, t, nonfinite, rep);
+}
+
+}  // extern "C"
+
+// The rows of a packed call, checked on the host before anything is queued: row u holds len[u] samples of
+// `format` at out[offsets[u] ..] (offsets null: tight packing in order); a row with len[u] < 0 is absent
+// (an idle voice: its offset is not looked at).  base[u]: the row's start (0 for an absent row), *span: the
+// samples out reaches over.  Rows may abut and may not overlap; a row without samples overlaps nothing.
+static afs_status packed_rows(afs_ctx *c, const char *fn, int32_t format, const void *out, const int64_t *offsets,
+                              const std::vector<int64_t> &len, std::vector<int64_t> *base, int64_t *span) {
+  if (format != AFS_SAMPLE_I16 && format != AFS_SAMPLE_F32)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: format %d is neither AFS_SAMPLE_I16 nor AFS_SAMPLE_F32", fn, format);
+  if (offsets && is_device_ptr(offsets)) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: offsets is a host array", fn);
+  const size_t B = len.size();
+  base->assign(B, 0);
+  *span = 0;
+  int64_t total = 0;
+  std::vector<std::pair<int64_t, int64_t>> rows;  // (start, samples) of the rows that hold any
+  for (size_t u = 0; u < B; ++u) {
+    if (len[u] < 0) continue;
+    const int64_t at = offsets ? offsets[u] : total;
+    if (at < 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: offsets[%d] = %lld is negative", fn, (int)u, (long long)at);
+    (*base)[u] = at;
+    total += len[u];
+    if (len[u] > 0) {
+      rows.emplace_back(at, len[u]);
+      *span = std::max(*span, at + len[u]);
+    }
+  }
+  if (offsets) {
+    std::sort(rows.begin(), rows.end());
+    for (size_t i = 1; i < rows.size(); ++i)
+      if (rows[i - 1].first + rows[i - 1].second > rows[i].first)
+        return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: the rows at offsets %lld (%lld samples) and %lld overlap", fn,
+                    (long long)rows[i - 1].first, (long long)rows[i - 1].second, (long long)rows[i].first);
+  }
+  if (total > 0 && (!out || (reinterpret_cast<uintptr_t>(out) & (sample_bytes(format) - 1))))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: out is NULL or not aligned to its sample type", fn);
+  return AFS_OK;
+}
+
+extern "C" {
+
+afs_status afs_synthesize_f32(afs_ctx *c, const afs_frame *frames, const uint32_t *seeds, int32_t B, int32_t F,
+                              int32_t hop, float *f32, int64_t fstride, uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  const char *fn = "afs_synthesize_f32";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!frames || B <= 0 || F < 2 || hop < 1)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, batch>0, num_frames>=2, hop>=1", fn);
+  Trajectories t;
+  t.frames = frames, t.fstride = t.F = F;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.ostride = (int64_t)(F - 1) * hop;
+  if (!f32 || (reinterpret_cast<uintptr_t>(f32) & 3))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: f32 is NULL or not float-aligned", fn);
+  if (fstride < t.ostride)
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: f32_stride %lld below the utterances' %lld samples", fn,
+                (long long)fstride, (long long)t.ostride);
+  t.pcm = f32, t.pstride = fstride, t.format = AFS_SAMPLE_F32;
+  t.samples = (int64_t)B * t.ostride;
+  return synth_core(c, t, nonfinite, rep);
+}
+
+afs_status afs_ragged_offsets(const int32_t *num_frames, int32_t B, int32_t hop, int64_t *offsets) {
+  if ((!num_frames && B > 0) || !offsets || B < 0 || hop < 1) return AFS_ERR_INVALID_ARGUMENT;
+  for (int32_t u = 0; u < B; ++u)
+    if (num_frames[u] < 1) return AFS_ERR_INVALID_ARGUMENT;
+  int64_t at = 0;
+  for (int32_t u = 0; u < B; ++u) {
+    offsets[u] = at;
+    at += (int64_t)(num_frames[u] - 1) * hop;
+  }
+  offsets[B] = at;
+  return AFS_OK;
+}
+
+afs_status afs_synthesize_ragged_packed(afs_ctx *c, const afs_frame *frames, int64_t fstride, const int32_t *num_frames,
+                                        const uint32_t *seeds, int32_t B, int32_t hop, int32_t format, void *out,
+                                        const int64_t *offsets, uint8_t *nonfinite, afs_report *rep) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  const char *fn = "afs_synthesize_ragged_packed";
+  if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
+  if (!frames || B <= 0 || hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frames, batch>0, hop>=1", fn);
+  if (!num_frames || is_device_ptr(num_frames))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
+  Trajectories t;
+  std::vector<int64_t> len((size_t)B), base;
+  for (int32_t u = 0; u < B; ++u) {
+    const int32_t F = num_frames[u];
+    if (F < 2 || F > fstride)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames[%d] = %d outside 2..frame_stride = %lld", fn, u, F,
+                  (long long)fstride);
+    t.F = std::max(t.F, F);
+    len[(size_t)u] = (int64_t)(F - 1) * hop;
+    t.samples += len[(size_t)u];
+  }
+  const afs_status s = packed_rows(c, fn, format, out, offsets, len, &base, &t.span);
+  if (s != AFS_OK) return s;
+  t.ostride = (int64_t)(t.F - 1) * hop;
+  t.frames = frames, t.fstride = fstride, t.num_frames = num_frames;
+  t.seeds = seeds, t.B = B, t.hop = hop;
+  t.pcm = out, t.pstride = 0, t.format = format, t.row_base = base.data();
   return synth_core(c, t, nonfinite, rep);
 }
 
@@ -1267,13 +1393,15 @@ struct PoolArrays {
   const int32_t *count = nullptr, *latched = nullptr;
 };
 static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *num_frames, const int32_t *trans, int upb,
-                              int hop, SynthCall *call, PoolArrays *pa) {
+                              int hop, SynthCall *call, PoolArrays *pa, const int64_t *row_base = nullptr) {
   const int B = s->B;
   const afs::RaggedOrder ro = afs::pool_order(trans, B, upb, hop);
   const size_t slots = ro.order.size();
   const size_t end_bytes = (size_t)ro.grid * sizeof(int64_t), slot_bytes = slots * sizeof(int32_t);
   const size_t row_bytes = (size_t)B * sizeof(int32_t);
-  const size_t bytes = end_bytes + 2 * slot_bytes + 3 * row_bytes;
+  // (a packed call's row starts ride behind the per-voice arrays, on an 8-byte boundary)
+  const size_t base0 = (end_bytes + 2 * slot_bytes + 3 * row_bytes + 7) / 8 * 8;
+  const size_t bytes = base0 + (row_base ? (size_t)B * sizeof(int64_t) : 0);
   if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
   else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
   HIP_TRY(c, c->ragged_host.reserve(bytes));
@@ -1287,8 +1415,10 @@ static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *n
   std::memcpy(h + rows0 + row_bytes, num_frames, row_bytes);
   int32_t *lat = (int32_t *)(h + rows0 + 2 * row_bytes);
   for (int u = 0; u < B; ++u) lat[u] = s->latch[(size_t)u] ? 1 : 0;
+  if (row_base) std::memcpy(h + base0, row_base, (size_t)B * sizeof(int64_t));
   HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
+  call->row_base = row_base ? (const int64_t *)(d + base0) : nullptr;
   call->ragged.block_end = (const int64_t *)d;
   call->so.order = (const int32_t *)(d + end_bytes);
   call->so.grid = ro.grid;
@@ -1299,15 +1429,17 @@ static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *n
   return AFS_OK;
 }
 
-// afs_session_synthesize_ragged (taps_out or null), afs_session_synthesize_ragged_pcm (pcm, out null).
+// afs_session_synthesize_ragged (taps_out or null), afs_session_synthesize_ragged_pcm (pcm, out null),
+// afs_session_synthesize_ragged_packed (packed: pcm holds samples of `format`, voice u's at offsets[u]).
 // One SynthCall on the session's state over the call's frame rows (launch_pool_rows): voice u plays
 // trans[u] transitions -- its count, less one while it is unlatched -- ntrans the largest; K1's blocks
 // come from pool_order, so a voice without a transition is in no slot, K5 skips its row and K6 returns
 // at once: nothing of it is read or written.
 static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *frames, int64_t fstride,
                             const int32_t *num_frames, int32_t hop, double *out, int64_t ostride, double *taps_out,
-                            int16_t *pcm, int64_t pstride, bool want_pcm, uint8_t *nonfinite, int32_t *produced,
-                            afs_report *rep) {
+                            void *pcm, int64_t pstride, bool want_pcm, uint8_t *nonfinite, int32_t *produced,
+                            afs_report *rep, int32_t format = AFS_SAMPLE_I16, bool packed = false,
+                            const int64_t *offsets = nullptr) {
   if (!s) return AFS_ERR_INVALID_ARGUMENT;
   afs_ctx *c = s->ctx;
   if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
@@ -1333,7 +1465,15 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   }
   const int64_t Tmax = (int64_t)ntrans * hop;
   if (any && !frames) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: frames is NULL", fn);
-  if (want_pcm) {
+  // (a packed call: the rows at the caller's offsets, or tight in voice order; an idle voice has no row)
+  std::vector<int64_t> row_base;
+  int64_t span = 0;
+  if (packed) {
+    std::vector<int64_t> len((size_t)B);
+    for (int u = 0; u < B; ++u) len[(size_t)u] = num_frames[u] == 0 ? -1 : (int64_t)trans[(size_t)u] * hop;
+    const afs_status ps = packed_rows(c, fn, format, pcm, offsets, len, &row_base, &span);
+    if (ps != AFS_OK) return ps;
+  } else if (want_pcm) {
     if (pstride < Tmax)
       return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: pcm_stride %lld below the %lld samples a voice produces", fn,
                   (long long)pstride, (long long)Tmax);
@@ -1373,7 +1513,8 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   PoolArrays pa;
   const int upb = s->lanes == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB;
   call.so = plain_order(c);
-  if ((st = pool_layout(c, s, num_frames, trans.data(), upb, hop, &call, &pa)) != AFS_OK) return st;
+  if ((st = pool_layout(c, s, num_frames, trans.data(), upb, hop, &call, &pa, packed ? row_base.data() : nullptr)) != AFS_OK)
+    return st;
   const size_t had = c->pool_rows.capacity();
   HIP_TRY(c, c->pool_rows.reserve((size_t)B * (size_t)(fstride + 1) * sizeof(afs_frame)));
   // (a new block once, zeroed: K5 stages frame 0 of every row of a block's run, a voice's without a
@@ -1390,17 +1531,17 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   // (a host out, taps_out or pcm goes up first and comes back whole: what lies outside the samples a
   // voice produces is the caller's)
   Staged<double> dout, dtaps;
-  Staged<int16_t> dpcm;
+  Staged<char> dpcm;
   const size_t out_bytes = (size_t)B * (size_t)ostride * sizeof(double);
   if ((st = dout.stage(c, out, out_bytes, c->stage_out, true)) != AFS_OK) return st;
   if ((st = dtaps.stage(c, taps_out, out_bytes * (size_t)c->n_taps, c->stage_taps, true)) != AFS_OK) return st;
-  const size_t pcm_bytes = ((size_t)(B - 1) * (size_t)pstride + (size_t)Tmax) * sizeof(int16_t);
-  if ((st = dpcm.stage(c, pcm, pcm_bytes, c->stage_pcm, true)) != AFS_OK) return st;
+  const size_t pcm_samples = packed ? (size_t)span : (size_t)(B - 1) * (size_t)pstride + (size_t)Tmax;
+  if ((st = dpcm.stage(c, (char *)pcm, pcm_samples * sample_bytes(format), c->stage_pcm, true)) != AFS_OK) return st;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   call.frames = rows, call.fstride = fstride + 1, call.rows = B;
   call.ntrans = ntrans, call.hop = hop;
   call.out = dout.dev, call.ostride = ostride;
-  call.pcm = dpcm.dev, call.pstride = pstride;
+  call.pcm = dpcm.dev, call.pstride = pstride, call.format = format;
   call.taps.out = dtaps.dev, call.taps.stride = ostride;
   call.ws = s->ws.data(), call.rng = s->rng.as<int32_t>(), call.lanes = s->tree_lanes.data();
   call.bp = s->bp, call.B = B, call.width = s->lanes;
@@ -1690,6 +1831,14 @@ afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *fr
                                              uint8_t *nonfinite, int32_t *produced, afs_report *rep) {
   return pool_core(s, "afs_session_synthesize_ragged_pcm", frames, frame_stride, num_frames, hop, nullptr, 0, nullptr,
                    pcm, pcm_stride, true, nonfinite, produced, rep);
+}
+
+afs_status afs_session_synthesize_ragged_packed(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                                const int32_t *num_frames, int32_t hop, int32_t format, void *out,
+                                                const int64_t *offsets, uint8_t *nonfinite, int32_t *produced,
+                                                afs_report *rep) {
+  return pool_core(s, "afs_session_synthesize_ragged_packed", frames, frame_stride, num_frames, hop, nullptr, 0, nullptr,
+                   out, 0, true, nonfinite, produced, rep, format, true, offsets);
 }
 
 afs_status afs_af_to_frames(afs_ctx *c, const double *params, int64_t n, afs_frame *frames) {

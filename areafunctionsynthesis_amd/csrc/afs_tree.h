@@ -161,10 +161,17 @@ hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out,
 // doubles, read only; K1 stored them with TreeArgs::out = flow, out_stride = p25_stride = win_stride),
 // the audio written as int16 (afs_audio.h sample_to_int16) to pcm[u * pcm_stride + i], i < n, and
 // nowhere else; pcm at any 2-byte alignment.  skip_claims, row_hops: as launch_tree_output.
-hipError_t launch_tree_output_pcm(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
-                                  int64_t n, int B, const double *p25, int skin, int16_t *pcm, int64_t pcm_stride,
-                                  hipStream_t st, const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0,
-                                  const int32_t *row_hops = nullptr, int hop = 0, int64_t s_begin = 0);
+// The one launch of every sample format and row layout: `samples` is the call's destination (int16_t or
+// float by `format`, AFS_SAMPLE_I16 / AFS_SAMPLE_F32: sample_to_f32, rows at any 4-byte alignment) and
+// this launch's samples start s_begin into each row -- row u at samples + u * stride, or with row_base
+// (a device array of B row starts in samples; ragged launches only) at samples + row_base[u], the packed
+// layout.  A ragged float32 launch takes row_base (strided rows: row_base[u] = u * stride); any other
+// combination is hipErrorInvalidValue.
+hipError_t launch_tree_output_samples(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
+                                      int64_t n, int B, const double *p25, int skin, int format, void *samples,
+                                      int64_t stride, const int64_t *row_base, hipStream_t st,
+                                      const uint32_t *skip_claims = nullptr, int64_t skip_cap = 0,
+                                      const int32_t *row_hops = nullptr, int hop = 0, int64_t s_begin = 0);
 // Load the tree kernels' and K5's code objects on the current device (afs_create: no code-object
 // load inside the first synthesis call).
 hipError_t preload_tree_kernels();

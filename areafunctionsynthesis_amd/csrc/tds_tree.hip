@@ -130,6 +130,62 @@ __global__ void __launch_bounds__(64) tree_output_pcm_ragged_kernel(const Tables
   else output_filter_run_pcm<false, 3>(X, tab->consts, f, (int)n, nullptr, o);
 }
 
+// K6 of the _f32 call: tree_output_pcm_kernel with the float32 sink (sample_to_f32, tree_core.h F32Pack):
+// f32[u * f32_stride + i], i < n, rows at any 4-byte alignment.  FORM 4.
+__global__ void __launch_bounds__(64) tree_output_f32_kernel(const Tables *tab, double *lds_state, const double *flow,
+                                                             int64_t win_stride, int64_t n, int B, const double *p25,
+                                                             int skin, const uint32_t *skip_claims, int64_t skip_cap,
+                                                             float *f32, int64_t f32_stride) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  const double *f = flow + (int64_t)u * win_stride;
+  float *o = f32 + (int64_t)u * f32_stride;
+  if (p25 && skin) output_filter_run_f32<true, 4>(X, tab->consts, f, (int)n, p25 + (int64_t)u * win_stride, o);
+  else output_filter_run_f32<false, 4>(X, tab->consts, f, (int)n, nullptr, o);
+}
+// K6 of the packed ragged calls: as tree_output_pcm_ragged_kernel, but utterance u's row of the call starts
+// at sample row_base[u] of the caller's buffer (any order, any alignment of the sample type) instead of
+// u * pcm_stride, so this launch's samples go to row_base[u] + s_begin + i, i < n.  FORM 5 (int16), 6 (float32).
+__global__ void __launch_bounds__(64) tree_output_pcm_packed_kernel(const Tables *tab, double *lds_state,
+                                                                    const double *flow, int64_t win_stride, int64_t n,
+                                                                    int B, const double *p25, int skin,
+                                                                    const uint32_t *skip_claims, int64_t skip_cap,
+                                                                    int16_t *pcm, const int64_t *row_base,
+                                                                    const int32_t *row_hops, int hop, int64_t s_begin) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  const int64_t left = (int64_t)row_hops[u] * hop - s_begin;
+  n = left < n ? left : n;
+  if (n <= 0) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  const double *f = flow + (int64_t)u * win_stride;
+  int16_t *o = pcm + row_base[u] + s_begin;
+  if (p25 && skin) output_filter_run_pcm<true, 5>(X, tab->consts, f, (int)n, p25 + (int64_t)u * win_stride, o);
+  else output_filter_run_pcm<false, 5>(X, tab->consts, f, (int)n, nullptr, o);
+}
+// (a strided ragged float32 row is this kernel's with row_base[u] = u * stride)
+__global__ void __launch_bounds__(64) tree_output_f32_packed_kernel(const Tables *tab, double *lds_state,
+                                                                    const double *flow, int64_t win_stride, int64_t n,
+                                                                    int B, const double *p25, int skin,
+                                                                    const uint32_t *skip_claims, int64_t skip_cap,
+                                                                    float *f32, const int64_t *row_base,
+                                                                    const int32_t *row_hops, int hop, int64_t s_begin) {
+  const int u = blockIdx.x * 64 + threadIdx.x;
+  if (u >= B) return;
+  if (skip_claims && (int64_t)*skip_claims > skip_cap) return;
+  const int64_t left = (int64_t)row_hops[u] * hop - s_begin;
+  n = left < n ? left : n;
+  if (n <= 0) return;
+  double *X = lds_state + (int64_t)u * X_TOTAL;
+  const double *f = flow + (int64_t)u * win_stride;
+  float *o = f32 + row_base[u] + s_begin;
+  if (p25 && skin) output_filter_run_f32<true, 6>(X, tab->consts, f, (int)n, p25 + (int64_t)u * win_stride, o);
+  else output_filter_run_f32<false, 6>(X, tab->consts, f, (int)n, nullptr, o);
+}
+
 // seeds == nullptr: utterance u is seeded u + 1 (afs.h)
 template <int W>
 __global__ void tree_reset_kernel(Lane<W> *lanes, double *lds, int B, const uint32_t *seeds) {
@@ -222,17 +278,34 @@ hipError_t launch_tree_output(const Tables *tab, double *lds_state, double *out,
   return hipGetLastError();
 }
 
-hipError_t launch_tree_output_pcm(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
-                                  int64_t n, int B, const double *p25, int skin, int16_t *pcm, int64_t pcm_stride,
-                                  hipStream_t st, const uint32_t *skip_claims, int64_t skip_cap,
-                                  const int32_t *row_hops, int hop, int64_t s_begin) {
+hipError_t launch_tree_output_samples(const Tables *tab, double *lds_state, const double *flow, int64_t win_stride,
+                                      int64_t n, int B, const double *p25, int skin, int format, void *samples,
+                                      int64_t stride, const int64_t *row_base, hipStream_t st,
+                                      const uint32_t *skip_claims, int64_t skip_cap, const int32_t *row_hops, int hop,
+                                      int64_t s_begin) {
   if (B <= 0 || n <= 0) return hipSuccess;
-  if (row_hops)
-    hipLaunchKernelGGL(tree_output_pcm_ragged_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, flow,
-                       win_stride, n, B, p25, skin, skip_claims, skip_cap, pcm, pcm_stride, row_hops, hop, s_begin);
+  const bool f32 = format == AFS_SAMPLE_F32;
+  // (row_base belongs to a ragged launch; a ragged float32 launch has no strided kernel and needs one)
+  if ((!f32 && format != AFS_SAMPLE_I16) || (row_base && !row_hops) || (f32 && row_hops && !row_base))
+    return hipErrorInvalidValue;
+  const dim3 grid((B + 63) / 64), block(64);
+  int16_t *pcm = (int16_t *)samples;
+  float *flt = (float *)samples;
+  if (row_base && f32)
+    hipLaunchKernelGGL(tree_output_f32_packed_kernel, grid, block, 0, st, tab, lds_state, flow, win_stride, n, B, p25,
+                       skin, skip_claims, skip_cap, flt, row_base, row_hops, hop, s_begin);
+  else if (row_base)
+    hipLaunchKernelGGL(tree_output_pcm_packed_kernel, grid, block, 0, st, tab, lds_state, flow, win_stride, n, B, p25,
+                       skin, skip_claims, skip_cap, pcm, row_base, row_hops, hop, s_begin);
+  else if (f32)
+    hipLaunchKernelGGL(tree_output_f32_kernel, grid, block, 0, st, tab, lds_state, flow, win_stride, n, B, p25, skin,
+                       skip_claims, skip_cap, flt + s_begin, stride);
+  else if (row_hops)
+    hipLaunchKernelGGL(tree_output_pcm_ragged_kernel, grid, block, 0, st, tab, lds_state, flow, win_stride, n, B, p25,
+                       skin, skip_claims, skip_cap, pcm + s_begin, stride, row_hops, hop, s_begin);
   else
-    hipLaunchKernelGGL(tree_output_pcm_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tab, lds_state, flow, win_stride,
-                       n, B, p25, skin, skip_claims, skip_cap, pcm, pcm_stride);
+    hipLaunchKernelGGL(tree_output_pcm_kernel, grid, block, 0, st, tab, lds_state, flow, win_stride, n, B, p25, skin,
+                       skip_claims, skip_cap, pcm + s_begin, stride);
   return hipGetLastError();
 }
 
@@ -352,7 +425,8 @@ hipError_t preload_tree_kernels() {
                        preload_one(tree_synth_kernel<AFS_GLOTTIS_TWO_MASS, false, 64>),
                        preload_one(tree_output_kernel), preload_one(tree_reset_kernel<TW>),
                        preload_one(tree_reset_kernel<64>), preload_one(tree_nonfinite_kernel),
-                       preload_one(tree_draws_kernel)})
+                       preload_one(tree_draws_kernel), preload_one(tree_output_f32_kernel),
+                       preload_one(tree_output_pcm_packed_kernel), preload_one(tree_output_f32_packed_kernel)})
     if (e == hipSuccess) e = x;
   return e;
 }

@@ -2174,7 +2174,7 @@ AFS_HD inline double output_filter_one(double *X, const Consts &C, double flow) 
 // FORM: a tag only -- a second kernel of a file takes an instantiation of its own (tds_tree.hip, K6 of
 // the ragged calls), so that each kernel stays the one caller of its copy and is compiled as before.
 // SINK: where sample t of the run goes, sink.put(t, sample), called once per sample in order of t
-// (OutInPlace: back over its flow; PcmPack: as int16 into the caller's row).
+// (OutInPlace: back over its flow; PcmPack: as int16 into the caller's row; F32Pack: as float32).
 struct OutInPlace {
   double *o;
   AFS_HD void put(int t, double smp) const { o[t] = smp; }
@@ -2205,6 +2205,34 @@ struct PcmPack {
     if (((t - head) & 7) == 7) {
       const uint64_t w[2] = {lo, hi};
       __builtin_memcpy(__builtin_assume_aligned(pcm + (t - 7), 16), w, 16);
+    }
+  }
+};
+
+// The float32 samples of a run of n, sample_to_f32 of each, into row[0 .. n) -- a row of the caller's at
+// any 4-byte alignment (a packed row starts wherever the one before it ended) -- and nothing outside it.
+// PcmPack's scheme at 4 samples per 16 bytes: the samples [head, tail) pass through four registers
+// (the oldest first: the lowest address) and go out as one 16-byte store whenever the row's address
+// reaches a 16-byte boundary; the samples before the first boundary and after the last go out one by one.
+struct F32Pack {
+  float *row;
+  int head, tail;  // samples [head, tail) are stored in groups of 4 from the 16-byte aligned row + head
+  float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+  AFS_HD F32Pack(float *p, int n) : row(p) {
+    const int h = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+    head = h < n ? h : n;
+    tail = head + (n - head) / 4 * 4;
+  }
+  AFS_HD void put(int t, double smp) {
+    const float v = sample_to_f32(smp);
+    if (t < head || t >= tail) {
+      row[t] = v;
+      return;
+    }
+    w0 = w1, w1 = w2, w2 = w3, w3 = v;
+    if (((t - head) & 3) == 3) {
+      const float w[4] = {w0, w1, w2, w3};
+      __builtin_memcpy(__builtin_assume_aligned(row + (t - 3), 16), w, 16);
     }
   }
 };
@@ -2323,6 +2351,13 @@ template <bool TONE, int FORM>
 AFS_HD inline void output_filter_run_pcm(double *X, const Consts &C, const double *flow, int n, const double *p25,
                                          int16_t *pcm) {
   PcmPack sink(pcm, n);
+  output_filter_run_to<TONE, FORM>(X, C, flow, n, p25, sink);
+}
+// ... the float32 form (K6 of the _f32 and packed float32 calls): the same with the audio to f32[0..n)
+template <bool TONE, int FORM>
+AFS_HD inline void output_filter_run_f32(double *X, const Consts &C, const double *flow, int n, const double *p25,
+                                         float *f32) {
+  F32Pack sink(f32, n);
   output_filter_run_to<TONE, FORM>(X, C, flow, n, p25, sink);
 }
 

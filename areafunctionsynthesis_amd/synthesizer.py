@@ -6,6 +6,9 @@
   an ``afs_session`` whose state stays on the GPU.
 * :meth:`Context.synthesize` -- whole trajectories (latch frame 0, then ``F-1`` calls of
   ``hop`` samples) for ``B`` utterances in one go.
+* :meth:`Context.synthesize_ragged` -- the same for utterances of different lengths; with
+  ``packed=True`` the rows come back without padding, as one flat int16 or float32 array plus offsets
+  (:func:`ragged_offsets`).
 * :meth:`Context.synthesize_stream` -- continuous batching: a corpus streamed through a pool of
   voices (:meth:`Synthesizer.synthesize_frames`, :meth:`Synthesizer.restart`), a few frames per
   voice and call.
@@ -73,6 +76,84 @@ def _pcm_rows(out, B: int):
     if not exact or (width > 1 and inner != 1) or (B > 1 and row < width):
         raise ValueError("a PCM out needs adjacent samples in rows that do not overlap")
     return addr, (row if B > 1 else max(row, width))
+
+
+def _sample_rows(out, B: int, dtype):
+    """:func:`_pcm_rows` for a destination of ``dtype`` samples (int16 or float32): (address, row stride)."""
+    if dtype == np.int16:
+        return _pcm_rows(out, B)
+    if len(out.shape) != 2 or int(out.shape[0]) != B:
+        raise ValueError("a float32 out must be float32 [B, samples]")
+    if isinstance(out, np.ndarray):
+        if out.dtype != np.float32:
+            raise ValueError("a float32 out must be float32")
+        inner, row = out.strides[1] // 4, out.strides[0] // 4
+        exact = out.strides[1] % 4 == 0 and out.strides[0] % 4 == 0
+        addr = int(out.ctypes.data)
+    else:
+        if "float32" not in str(out.dtype):
+            raise ValueError("a float32 out must be float32")
+        inner, row, exact = int(out.stride(1)), int(out.stride(0)), True
+        addr = int(out.data_ptr())
+    width = int(out.shape[1])
+    if not exact or (width > 1 and inner != 1) or (B > 1 and row < width):
+        raise ValueError("a float32 out needs adjacent samples in rows that do not overlap")
+    return addr, (row if B > 1 else max(row, width))
+
+
+def _sample_format(pcm: bool, f32: bool, packed: bool = False):
+    """(afs_sample_format, numpy dtype) of a call's ``pcm`` / ``f32`` switches, None for the float64 call."""
+    if pcm and f32:
+        raise ValueError("pcm and f32 are two sample formats: choose one")
+    if packed and not (pcm or f32):
+        raise ValueError("packed needs pcm=True or f32=True: there is no packed float64 form (the float64 rows "
+                         "are written by the synthesis kernel itself, not by the output stage)")
+    if f32:
+        return _native.AFS_SAMPLE_F32, np.float32
+    if pcm:
+        return _native.AFS_SAMPLE_I16, np.int16
+    return None, np.float64
+
+
+def ragged_offsets(num_frames, hop: int) -> np.ndarray:
+    """afs_ragged_offsets: int64[B + 1], the exclusive prefix sum of ``(num_frames[u]-1)*hop`` with the total
+    last -- the tight layout of a packed call; row u is ``flat[offsets[u]:offsets[u + 1]]``."""
+    counts = np.ascontiguousarray(num_frames, dtype=np.int32).reshape(-1)
+    off = np.zeros(counts.size + 1, dtype=np.int64)
+    _native.check(_native.load().afs_ragged_offsets(_vp(_addr(counts)), int(counts.size), int(hop), _vp(_addr(off))),
+                  None, "afs_ragged_offsets")
+    return off
+
+
+def _packed_out(out, offsets, lengths, dtype):
+    """The destination and row starts of a packed call: (out, its address, offsets int64[B + 1] or [B], the
+    host array of row starts to pass or None for tight packing).  ``lengths[u]``: row u's samples (None: the
+    row is absent).  ``out=None``: a numpy array of the span; ``offsets=None``: tight in order."""
+    B = len(lengths)
+    own = None
+    if offsets is None:
+        off = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum([0 if n is None else int(n) for n in lengths], out=off[1:])
+        span = int(off[B])
+    else:
+        own = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if own.size not in (B, B + 1):
+            raise ValueError("offsets must hold one row start per utterance")
+        off = own
+        own = np.ascontiguousarray(own[:B])
+        span = max([0] + [int(own[u]) + int(n) for u, n in enumerate(lengths) if n])
+    if out is None:
+        out = np.zeros(span, dtype=dtype)
+    if len(out.shape) != 1:
+        raise ValueError("a packed out is 1-D")
+    if isinstance(out, np.ndarray):
+        if out.dtype != dtype or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"a packed out must be contiguous {np.dtype(dtype).name}")
+    elif np.dtype(dtype).name not in str(out.dtype) or (out.shape[0] > 1 and int(out.stride(0)) != 1):
+        raise ValueError(f"a packed out must be contiguous {np.dtype(dtype).name}")
+    if int(out.shape[0]) < span:
+        raise ValueError(f"a packed out must hold {span} samples")
+    return out, (_addr(out) if int(out.shape[0]) else 0), off, own
 
 
 class Context:
@@ -157,7 +238,7 @@ class Context:
         return {"total_bytes": int(m.total_bytes), "sample_buffer_bytes": int(m.sample_buffer_bytes)}
 
     def synthesize(self, frames, hop: int, seeds=None, out=None, report: bool = False, nonfinite=None,
-                   taps=False, taps_out=None, pcm: bool = False):
+                   taps=False, taps_out=None, pcm: bool = False, f32: bool = False):
         """frames[B, F] (FRAME_DTYPE array, or a uint8 torch tensor [B, F, 1072] on the GPU)
         -> audio[B, (F-1)*hop] float64.  ``seeds=None``: 1 .. B.  ``nonfinite``: optional uint8
         array / tensor of B flags (1 = the utterance's audio holds NaN/Inf); with ``report``
@@ -166,7 +247,11 @@ class Context:
         (``taps_out``: a numpy array or GPU tensor to receive them) -- and with ``report``
         ``(audio, taps, report)``.  ``pcm=True``: the audio as int16[B, T] (afs_synthesize_pcm: bit
         for bit :meth:`to_int16` of the float64 audio, which is then never stored); ``out`` may be an
-        int16 numpy array or GPU tensor [B, T] with strided rows.  No taps with ``pcm``."""
+        int16 numpy array or GPU tensor [B, T] with strided rows.  No taps with ``pcm``.  ``f32=True``:
+        the audio as float32[B, T] likewise (afs_synthesize_f32: bit for bit ``np.float32`` of the float64
+        audio, non-finite values included); ``pcm`` and ``f32`` together is an error."""
+        fmt, dtype = _sample_format(pcm, f32)
+        pcm = fmt is not None  # (below: a call of the sample-format family)
         if pcm and taps:
             raise ValueError("the PCM calls have no taps")
         if isinstance(frames, np.ndarray):
@@ -184,11 +269,11 @@ class Context:
         if isinstance(seeds, np.ndarray):
             seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         if out is None:
-            out = np.zeros((B, T), dtype=np.int16 if pcm else np.float64)
+            out = np.zeros((B, T), dtype=dtype)
         if pcm:
             if tuple(out.shape) != (B, T):
-                raise ValueError("a PCM out must be int16 [B, (F-1)*hop]")
-            pcm_addr, pcm_stride = _pcm_rows(out, B)
+                raise ValueError("a PCM or float32 out must be [B, (F-1)*hop]")
+            pcm_addr, pcm_stride = _sample_rows(out, B, dtype)
         elif _nbytes(out) != B * T * 8:
             raise ValueError("out must hold B*(F-1)*hop doubles")
         if nonfinite is None and report:
@@ -209,9 +294,10 @@ class Context:
                                                ctypes.byref(rep) if report else None)
             _native.check(st, self._h, "afs_synthesize_taps")
         elif pcm:
-            st = self._lib.afs_synthesize_pcm(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop, _vp(pcm_addr),
-                                              pcm_stride, _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
-            _native.check(st, self._h, "afs_synthesize_pcm")
+            name = "afs_synthesize_f32" if f32 else "afs_synthesize_pcm"
+            st = getattr(self._lib, name)(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop, _vp(pcm_addr),
+                                          pcm_stride, _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, name)
         else:
             st = self._lib.afs_synthesize(self._h, _vp(_addr(frames)), _vp(_addr(seeds)), B, F, hop,
                                           _vp(_addr(out)), _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
@@ -224,7 +310,8 @@ class Context:
         return res if len(res) > 1 else res[0]
 
     def synthesize_ragged(self, frames, num_frames, hop: int, seeds=None, out=None, report: bool = False,
-                          nonfinite=None, taps=False, taps_out=None, pcm: bool = False):
+                          nonfinite=None, taps=False, taps_out=None, pcm: bool = False, f32: bool = False,
+                          packed: bool = False, offsets=None):
         """:meth:`synthesize` for utterances of different lengths in one call (tree solver).
         ``frames``: a ``[B, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[B, Fmax, 1072]`` of which
         utterance u plays the first ``num_frames[u]`` frames (the rest is never read), or a list of
@@ -235,7 +322,20 @@ class Context:
         appends them.  Row u is bit for bit ``synthesize(frames[u:u+1, :num_frames[u]], hop)`` with
         its seed.  Nothing is written past a row's end: an ``out`` allocated here is zero there.
         ``pcm=True``: the audio as int16 (afs_synthesize_ragged_pcm; ``out``: int16 ``[B, out_stride]``,
-        numpy or GPU tensor, rows may be strided); no taps."""
+        numpy or GPU tensor, rows may be strided); no taps.
+        ``packed=True`` with ``pcm=True`` or ``f32=True`` (afs_synthesize_ragged_packed): returns ``(flat,
+        offsets)`` (then the report) instead -- the rows without padding in one 1-D int16 or float32 array,
+        row u at ``flat[offsets[u]:offsets[u + 1]]``, ``offsets`` int64 ``[B + 1]`` (:func:`ragged_offsets`).
+        ``out``: a 1-D numpy array or GPU tensor of that dtype to receive them; ``offsets``: the caller's
+        own row starts ``[B]`` in samples, in any order and with gaps (returned as given; row u is
+        ``flat[offsets[u]:offsets[u] + (num_frames[u]-1)*hop]``, nothing else is written).  ``f32`` needs
+        ``packed``; there is no packed float64 form."""
+        fmt, dtype = _sample_format(pcm, f32, packed)
+        if f32 and not packed:
+            raise ValueError("a ragged float32 call is packed: pass packed=True")
+        if offsets is not None and not packed:
+            raise ValueError("offsets belong to a packed call")
+        pcm = fmt is not None
         if pcm and taps:
             raise ValueError("the PCM calls have no taps")
         if isinstance(frames, (list, tuple)):
@@ -265,6 +365,24 @@ class Context:
             seeds = np.arange(1, B + 1, dtype=np.uint32)
         if isinstance(seeds, np.ndarray):
             seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if nonfinite is None and report:
+            nonfinite = np.zeros(B, dtype=np.uint8)
+        if nonfinite is not None and _nbytes(nonfinite) != B:
+            raise ValueError("nonfinite must hold B bytes")
+        if packed:
+            if lengths is None:
+                raise ValueError("num_frames must hold B counts")
+            out, addr, off, own = _packed_out(out, offsets, [max(int(n), 0) for n in lengths], dtype)
+            rep = _native.AfsReport()
+            st = self._lib.afs_synthesize_ragged_packed(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                        _vp(_addr(seeds)), B, hop, fmt, _vp(addr), _vp(_addr(own)),
+                                                        _vp(_addr(nonfinite)), ctypes.byref(rep) if report else None)
+            _native.check(st, self._h, "afs_synthesize_ragged_packed")
+            if report:
+                return out, off, {"device_ms": rep.device_ms, "samples": rep.samples,
+                                  "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                                  "nonfinite": nonfinite}
+            return out, off
         if out is None:
             out = np.zeros((B, max(int(lengths.max()), 0) if lengths is not None else 0),
                            dtype=np.int16 if pcm else np.float64)
@@ -735,7 +853,8 @@ class Synthesizer:
         return f
 
     def synthesize_frames(self, frames, num_frames, hop: int, out=None, taps: bool = False, taps_out=None,
-                          pcm: bool = False, report: bool = False):
+                          pcm: bool = False, report: bool = False, f32: bool = False, packed: bool = False,
+                          offsets=None):
         """afs_session_synthesize_ragged: every voice plays its own number of frames in one call.
         ``frames``: a ``[batch, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[batch, Fmax, 1072]`` of
         which voice u plays the first ``num_frames[u]`` (the rest is never read), or a list of per-voice
@@ -746,7 +865,18 @@ class Synthesizer:
         ``produced``, or the row length of a given ``out`` (numpy or GPU tensor; nothing is written at or
         past ``produced[u]`` in row u) -- then the taps ``[batch, n_taps, out_stride]`` and the report as
         :meth:`Context.synthesize_ragged` appends them.  ``pcm=True``: int16 audio
-        (afs_session_synthesize_ragged_pcm; ``out``'s rows may be strided); no taps."""
+        (afs_session_synthesize_ragged_pcm; ``out``'s rows may be strided); no taps.
+        ``packed=True`` with ``pcm=True`` or ``f32=True`` (afs_session_synthesize_ragged_packed): returns
+        ``(flat, offsets, produced)`` (then the report) -- voice u's samples at ``flat[offsets[u]:offsets[u]
+        + produced[u]]`` of a 1-D int16 or float32 array, tightly in voice order (``offsets`` int64
+        ``[batch + 1]``), or at the caller's ``offsets[batch]`` (an idle voice's is not looked at); ``out``:
+        a 1-D numpy array or GPU tensor to receive them.  ``f32`` needs ``packed``."""
+        fmt, dtype = _sample_format(pcm, f32, packed)
+        if f32 and not packed:
+            raise ValueError("a float32 pool call is packed: pass packed=True")
+        if offsets is not None and not packed:
+            raise ValueError("offsets belong to a packed call")
+        pcm = fmt is not None
         if pcm and taps:
             raise ValueError("the PCM calls have no taps")
         B = self.batch
@@ -773,6 +903,24 @@ class Synthesizer:
             counts = np.ascontiguousarray(num_frames, dtype=np.int32)
             if counts.shape != (B,):
                 raise ValueError("num_frames must hold batch counts")
+        if packed:
+            if counts is None:
+                raise ValueError("num_frames must hold batch counts")
+            lat = self.latched.astype(np.int64)
+            lengths = [None if c == 0 else max(int(c) - 1 + int(l), 0) * int(hop) for c, l in zip(counts, lat)]
+            out, addr, off, own = _packed_out(out, offsets, lengths, dtype)
+            nonfinite = np.zeros(B, dtype=np.uint8) if report else None
+            rep = _native.AfsReport()
+            st = self._lib.afs_session_synthesize_ragged_packed(self._h, _vp(_addr(frames)), fstride, _vp(_addr(counts)),
+                                                                int(hop), fmt, _vp(addr), _vp(_addr(own)),
+                                                                _vp(_addr(nonfinite)), _vp(_addr(produced)),
+                                                                ctypes.byref(rep) if report else None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_ragged_packed")
+            if report:
+                return out, off, produced, {"device_ms": rep.device_ms, "samples": rep.samples,
+                                            "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                                            "nonfinite": nonfinite}
+            return out, off, produced
         if out is None:
             width = 0
             if counts is not None:

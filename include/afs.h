@@ -446,6 +446,57 @@ afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *fr
                                              const int32_t *num_frames, int32_t hop, int16_t *pcm,
                                              int64_t pcm_stride, uint8_t *nonfinite, int32_t *produced,
                                              afs_report *report);
+/* ---- Packed ragged output and float32 samples ----------------------------------------------
+ * The _pcm calls with two more freedoms: a row of the destination may start at an offset of its own
+ * instead of u*stride (no padding to the longest utterance), and the samples may be float32.
+ *
+ * afs_synthesize_f32: afs_synthesize_pcm with rows of float, f32[u*f32_stride + s] = (float)x of the
+ * fp64 call's sample x (round to nearest even; a NaN stays a NaN and an infinity an infinity, where
+ * the int16 form stores 0 and the clipped value).  f32 at any float alignment, f32_stride >= T.
+ *
+ * afs_synthesize_ragged_packed: afs_synthesize_ragged_pcm with row u at out[offsets[u] ..
+ * offsets[u] + T_u), T_u = (num_frames[u]-1)*hop.  format: AFS_SAMPLE_I16 (out is int16_t *, the
+ * _pcm calls' samples) or AFS_SAMPLE_F32 (float *, afs_synthesize_f32's).  out is host or device
+ * memory aligned to its sample type; offsets is a HOST array of batch row starts in samples, in any
+ * order and with any gaps, or NULL: tight packing in call order, row u at the sum of the T_v before it
+ * (afs_ragged_offsets).  Nothing outside the rows is written.  A host out spans max(offsets[u] + T_u)
+ * samples; it is uploaded first and copied back whole (the gaps are the caller's), through a staging
+ * buffer of that size.  A device out does not wait under AFS_ASYNC.  nonfinite, afs_rng_draws and
+ * report->samples are the strided call's.
+ *
+ * afs_ragged_offsets: offsets[batch + 1] = the exclusive prefix sum of (num_frames[u]-1)*hop, the
+ * total in the last entry: the tight layout, and the samples a packed buffer holds.  Needs no context
+ * (AFS_ERR_INVALID_ARGUMENT: a NULL array, batch < 0, hop < 1, a count below 1).
+ *
+ * afs_session_synthesize_ragged_packed: the voice pool's call (afs_session_synthesize_ragged_pcm) with
+ * voice u's produced[u] samples at out[offsets[u] ..].  An idle voice (count 0) writes nothing and its
+ * offset is not looked at; offsets == NULL packs the produced lengths tightly in voice order.  Packed,
+ * strided, int16, float32 and fp64 calls may alternate on one session.
+ *
+ * Every check is made on the host before anything is queued, and a refused call writes nothing.
+ * AFS_ERR_INVALID_ARGUMENT: an unknown format, a NULL or misaligned out when there are samples to
+ * write, a negative offset, two rows that overlap (rows may abut; rows without samples overlap
+ * nothing), offsets in device memory, and what the strided call refuses.  Tree solver only
+ * (AFS_ERR_UNSUPPORTED otherwise).
+ * Not covered: a packed fp64 form (the fp64 calls' rows are written by the synthesis kernel itself,
+ * not by the output stage), float32 or packed taps and the _taps calls, afs_multi_synthesize, target
+ * sequences, afs_synthesizer.hpp, a float32 afs_session_synthesize. */
+typedef enum afs_sample_format {
+  AFS_SAMPLE_I16 = 0, /* int16_t: afs_to_int16 of the fp64 sample */
+  AFS_SAMPLE_F32 = 1  /* float: (float) of the fp64 sample */
+} afs_sample_format;
+afs_status afs_synthesize_f32(afs_ctx *ctx, const afs_frame *frames, const uint32_t *seeds, int32_t batch,
+                              int32_t num_frames, int32_t hop, float *f32, int64_t f32_stride,
+                              uint8_t *nonfinite, afs_report *report);
+afs_status afs_synthesize_ragged_packed(afs_ctx *ctx, const afs_frame *frames, int64_t frame_stride,
+                                        const int32_t *num_frames, const uint32_t *seeds, int32_t batch,
+                                        int32_t hop, int32_t format, void *out, const int64_t *offsets,
+                                        uint8_t *nonfinite, afs_report *report);
+afs_status afs_ragged_offsets(const int32_t *num_frames, int32_t batch, int32_t hop, int64_t *offsets);
+afs_status afs_session_synthesize_ragged_packed(afs_session *s, const afs_frame *frames, int64_t frame_stride,
+                                                const int32_t *num_frames, int32_t hop, int32_t format, void *out,
+                                                const int64_t *offsets, uint8_t *nonfinite, int32_t *produced,
+                                                afs_report *report);
 /* Diagnostics: the device memory the context holds now (its buffers grow on demand and are kept).
  * total_bytes: all of it; sample_buffer_bytes: the part that holds one fp64 value per
  * utterance-sample -- the flow and section-25 windows of a launch, a staged fp64 out or taps of a host
@@ -453,7 +504,9 @@ afs_status afs_session_synthesize_ragged_pcm(afs_session *s, const afs_frame *fr
  * the two windows alone.  total_bytes counts the frame rows of a pool call
  * (afs_session_synthesize_ragged: batch x (frame_stride + 1) frames, kept by the context) and the
  * staging of voice records (afs_session_copy_voices, host records of _save_voices / _load_voices: n
- * records, grown on demand and kept); neither is a sample buffer. */
+ * records, grown on demand and kept); neither is a sample buffer.  It also counts what a packed or
+ * float32 call adds: the row starts on the device (8 B per utterance, beside the ragged layout) and the
+ * staging of a host destination (its span in samples of its format, in the int16 staging's buffer). */
 typedef struct afs_memory_info {
   int64_t total_bytes;
   int64_t sample_buffer_bytes;
