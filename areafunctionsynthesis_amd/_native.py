@@ -32,8 +32,11 @@ AFS_TAP_PRESSURE = 0
 AFS_TAP_CURRENT = 1
 AFS_SAMPLE_I16 = 0  # afs.h afs_sample_format
 AFS_SAMPLE_F32 = 1
+# afs_device_math.h afs_math_op
+MATH_OPS = {"RCP": 0, "SQRT": 1, "DIV": 2, "HOP_RATIO": 3, "AT_LEAST": 4, "AT_MOST": 5, "NONNEG": 6,
+            "DIPOLE_GAIN": 7, "NOISE_COEF": 8, "RCP_SEED": 9, "DIV_UNCORRECTED": 10, "SQRT_SHORT": 11}
 
-# Every symbol include/afs.h declares.
+# Every symbol include/afs.h and include/afs_device_math.h declare.
 EXPORTED = (
     "afs_abi_version", "afs_config_default", "afs_status_string", "afs_create", "afs_destroy",
     "afs_last_error", "afs_set_stream", "afs_lanes_per_utterance", "afs_synthesis_kernel", "afs_synchronize", "afs_synthesize",
@@ -50,6 +53,7 @@ EXPORTED = (
     "afs_session_latched",
     "afs_session_voice_state_bytes", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
     "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets", "afs_session_synthesize_ragged_packed",
+    "afs_device_math",
 )
 
 
@@ -197,6 +201,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_ragged_offsets.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
     lib.afs_session_synthesize_ragged_packed.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp,
                                                          vp, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_device_math.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64, vp]
+    lib.afs_device_math.restype = ctypes.c_int
     for name in ("afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
                  "afs_session_latched", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
                  "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets",

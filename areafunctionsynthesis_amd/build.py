@@ -25,7 +25,7 @@ LIB = os.path.join(HERE, "libafs.so")
 ARCH = os.environ.get("AFS_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["afs_capi.cpp", "afs_comm.cpp", "afs_tables.cpp", "tds_lane.hip", "tds_tree.hip", "tds_plan.hip",
-           "af_kernels.hip", "audio_kernels.hip", "session_kernels.hip"]
+           "af_kernels.hip", "audio_kernels.hip", "session_kernels.hip", "device_math.hip"]
 # The phase profiler (tools/phase_prof): the tree kernel's body with cycle counters, linked with
 # the library's own objects of the kernels and their tables.
 PROF_DIR = os.path.join(ROOT, "tools", "phase_prof")
@@ -54,7 +54,10 @@ PROF_SOURCES = ["afs_tables.cpp", "tds_tree.hip", "tds_plan.hip"]
 # and no comparison, product or sum in this kernel tells -0 from +0 except in a zero result (no
 # division by a possibly-zero value, no copysign).  A/B: profiles/r04n_nsz_ab.txt.
 TREE_FLAGS = ["-mllvm", "-disable-machine-licm", "-ffp-contract=fast-honor-pragmas", "-fno-signed-zeros", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-PER_SOURCE: dict = {"tds_tree.hip": list(TREE_FLAGS)}
+# The arithmetic probe (device_math.hip, afs_device_math) runs tree_core.h's device-only forms on their
+# own: it takes exactly TREE_FLAGS, so that a test of it measures the arithmetic as the synthesis
+# kernel's compilation makes it (contraction, no signed zeros).
+PER_SOURCE: dict = {"tds_tree.hip": list(TREE_FLAGS), "device_math.hip": list(TREE_FLAGS)}
 # (AFS_TREE_FLAGS: extra compiler flags for the tree kernel, for A/B builds of scheduler options)
 if os.environ.get("AFS_TREE_FLAGS"):
     PER_SOURCE["tds_tree.hip"] = TREE_FLAGS + os.environ["AFS_TREE_FLAGS"].split()
@@ -104,17 +107,42 @@ def deps_command(cmd: list) -> list:
     return rest[:i] + rest[i + 2:] + ["-M", "--cuda-host-only", "-MT", obj, "-MF", obj + ".d"]
 
 
-def depfile_sources(depfile: str) -> set:
-    """The files of this repository that a compiler's depfile names."""
+def _depfile_rules(depfile: str) -> list:
+    """A depfile's rules as (target, [dependencies]), the paths unescaped."""
     with open(depfile, encoding="utf-8") as fh:
         text = fh.read().replace("\\\n", " ")
-    deps = set()
+    rules = []
     for rule in text.splitlines():
-        for d in re.split(r"(?<!\\)\s+", rule.partition(": ")[2]):
-            d = os.path.normpath(d.replace("\\ ", " "))
+        target, sep, deps = rule.partition(": ")
+        if sep:
+            rules.append((target.replace("\\ ", " "), [d.replace("\\ ", " ") for d in re.split(r"(?<!\\)\s+", deps) if d]))
+    return rules
+
+
+def depfile_sources(depfile: str) -> set:
+    """The files of this repository that a compiler's depfile names (a relative path is one
+    below the repository's root: relocatable_depfile)."""
+    deps = set()
+    for _, names in _depfile_rules(depfile):
+        for d in names:
+            d = os.path.normpath(os.path.join(ROOT, d))  # (an absolute path stays what it is)
             if d.startswith(ROOT + os.sep):
                 deps.add(d)
     return deps
+
+
+def relocatable_depfile(depfile: str) -> None:
+    """Rewrite a compiler's depfile with the repository's own files named relative to its root:
+    the compiler writes absolute paths, and a built tree that is copied or moved elsewhere would
+    no longer know what its objects were built from (every object stale, and the include scan
+    with nothing to agree with)."""
+    def rel(p):
+        p = os.path.normpath(p)
+        return os.path.relpath(p, ROOT) if p.startswith(ROOT + os.sep) else p
+    esc = lambda p: p.replace(" ", "\\ ")  # noqa: E731
+    lines = [esc(rel(t)) + ": " + " \\\n  ".join(esc(rel(d)) for d in deps) + "\n" for t, deps in _depfile_rules(depfile)]
+    with open(depfile, "w", encoding="utf-8") as fh:
+        fh.writelines(lines)
 
 
 def stale_reason(cmd: list) -> str | None:
@@ -151,6 +179,7 @@ def _compile(cmd: list) -> None:
         os.remove(obj + ".cmd")
     _run(cmd)
     _run(deps_command(cmd))
+    relocatable_depfile(obj + ".d")
     with open(obj + ".cmd", "w", encoding="utf-8") as fh:
         fh.write("\n".join(cmd))
 

@@ -20,6 +20,7 @@
 #include "afs_lane.h"
 #include "afs_audio.h"
 #include "afs_ctx.h"
+#include "afs_device_math.h"
 #include "afs_model.h"
 #include "afs_ragged_order.h"
 #include "afs_session_kernels.h"
@@ -1251,6 +1252,24 @@ afs_status afs_tube_interpolate(afs_ctx *c, const afs_frame *fl, const afs_frame
   HIP_TRY(c, afs::launch_tree_interp(c->tab(), dl, dr, dratio, n, da, dlen, c->stream));
   HIP_TRY(c, hipMemcpyAsync(area, da, ob, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(length, dlen, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return AFS_OK;
+}
+
+afs_status afs_device_math(afs_ctx *c, int32_t op, const double *a, const double *b, int64_t n, double *out) {
+  if (!c) return AFS_ERR_INVALID_ARGUMENT;
+  if (c->cfg.solver != AFS_SOLVER_TREE) return fail(c, AFS_ERR_UNSUPPORTED, "afs_device_math: tree solver only");
+  if (op < 0 || op >= AFS_MATH_OP_COUNT || !a || !b || !out || n <= 0 || n > ((int64_t)1 << 31))
+    return fail(c, AFS_ERR_INVALID_ARGUMENT, "afs_device_math: need an afs_math_op, a, b, out, 0 < n <= 2^31");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const size_t nb = (size_t)n * 8;
+  afs::DeviceBuf tmp;
+  HIP_TRY(c, tmp.reserve(3 * nb));
+  double *da = tmp.as<double>(), *db = da + n, *dout = db + n;
+  HIP_TRY(c, hipMemcpyAsync(da, a, nb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(db, b, nb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, afs::launch_device_math(op, da, db, n, dout, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out, dout, nb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return AFS_OK;
 }

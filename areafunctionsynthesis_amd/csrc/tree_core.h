@@ -180,8 +180,10 @@ struct ArmCarry {
 struct D4 { double v[4]; };
 
 
-// 1/d for the pivots, areas and surfaces: v_rcp_f64 and one Newton step on the device (within
-// 11 ulps of the division, profiles/r02ad_f64_ops.txt).  A second step makes it exactly rounded;
+// 1/d for the pivots, areas and surfaces: v_rcp_f64 and one Newton step on the device: within
+// 11 ulps of the division for 2^-300 <= |d| <= 2^300 of either sign, and odd in d bit for bit
+// (tests/test_device_math_gpu.py::test_rcp_within_11_ulps_and_odd asserts both on this function
+// compiled as device code with the kernel's flags).  A second step makes it exactly rounded;
 // dropping it measured +2.3 % end to end (profiles/r03s_rcp_rows_ab.txt) with the parity
 // figures still 5-6 orders inside the bounds and 0 rand() count differences.
 // Plain division in the CPU emulator.
@@ -198,7 +200,10 @@ AFS_HD inline double pivot_recip(double d) {
 // Square root of a positive, finite, normal operand (areas, Q, masses x stiffnesses; the
 // inputs of this kernel are >= 1e-3): LLVM's correctly rounded f64 sequence (v_rsq_f64 and
 // Goldschmidt/Newton steps) without its range scaling and zero/infinity fix-up, bit-identical
-// to sqrt() for x >= 2^-767 (tools/microbench/f64_ops.hip checks 3M inputs).  About 40 of
+// to the IEEE square root for 2^-767 <= x < 2^1023
+// (tests/test_device_math_gpu.py::test_sqrt_is_the_ieee_square_root: structured mantissas, exact
+// squares, roots that all but tie between two doubles, random operands).  Nothing is claimed or tested
+// below 2^-767, where LLVM's sequence scales the operand first.  About 40 of
 // sqrt()'s 107 cycles of dependent latency are the parts left out.  Host builds call sqrt.
 AFS_HD inline double fast_sqrt(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -216,11 +221,13 @@ AFS_HD inline double fast_sqrt(double x) {
 #endif
 }
 
-// Reciprocal and quotient of positive, normal operands (areas, surfaces, capacitances) without
-// the scaling/fixup steps of IEEE division: v_rcp_f64 + one Newton step (pivot_recip: within 11
-// ulps of 1 / b), and for the quotient one residual correction (within 1 ulp of a / b for the
-// operands here, measured on 3 M inputs by tools/microbench/f64_ops.hip).  Host builds (the CPU
-// emulator) divide.
+// Reciprocal and quotient of normal operands (areas, surfaces, capacitances; the glottis determinant
+// and glottis_open_close_one's displacements come with either sign, the latter's numerator may be 0)
+// without the scaling/fixup steps of IEEE division: v_rcp_f64 + one Newton step (pivot_recip: within
+// 11 ulps of 1 / b), and for the quotient one residual correction: within 1 ulp of a / b for
+// 2^-100 <= |a|, |b| <= 2^100 under every sign combination, and a zero (of either sign) for a = 0
+// (tests/test_device_math_gpu.py::test_div_within_1_ulp, ::test_div_of_zero_is_zero).  Host builds
+// (the CPU emulator) divide.
 AFS_HD inline double fast_rcp(double d) { return pivot_recip(d); }
 AFS_HD inline double fast_div(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -235,9 +242,11 @@ AFS_HD inline double fast_div(double a, double b) {
 // The interpolation ratio i / hop of sample i of a hop (0 <= i < hop), from inv_hop = 1 / hop
 // (correctly rounded, once per launch): q = i * inv_hop, then one correction by the exact remainder
 // i - hop q (an fma): the correctly rounded quotient (Markstein's theorem), so bit for bit the
-// division the reference and K5 take (tests/test_hop_ratio.py checks every i < hop for every hop up
-// to 8192 and sampled hops up to 65536); one multiply and two fmas instead of the ~10 instructions of
-// an IEEE division on the sample's chain.  Host builds divide.
+// division the reference and K5 take (tests/test_hop_ratio.py checks the sequence on the host for every
+// i < hop for every hop up to 8192 and sampled hops up to 65536;
+// tests/test_device_math_gpu.py::test_hop_ratio_is_the_division checks this function as device code
+// with the kernel's flags for every hop up to 2048 and 441 .. 65536); one multiply and two fmas instead
+// of the ~10 instructions of an IEEE division on the sample's chain.  Host builds divide.
 AFS_HD inline double hop_ratio(int i, double dhop, double inv_hop) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double di = (double)i;
@@ -253,6 +262,8 @@ AFS_HD inline double hop_ratio(int i, double dhop, double inv_hop) {
 // `if (x < c) x = c`.  Device: one v_max_f64 / v_min_f64 (the select form is a compare and two
 // 32-bit selects of the constant's halves); equal for every x that is not a NaN (a NaN gives c --
 // the inputs here are areas, surfaces and controls, finite).  Host builds compare.
+// (tests/test_device_math_gpu.py::test_clamps_equal_the_select_forms: at_least, at_most and nonneg against
+// the select forms over zeros, subnormals, infinities and the kernel's constants, and the NaN results.)
 AFS_HD inline double at_least(double x, double c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_fmax(x, c);
@@ -404,7 +415,8 @@ AFS_HD inline void glottis_open_close(const double *gp, double cord, double rel0
 }
 
 // Gain of the glottis dipole source, 0.5e-7 * 10^(aspiration dB / 20) (TdsModel.cpp:1546),
-// evaluated with the glottis (off the constriction phase's chains).
+// evaluated with the glottis (off the constriction phase's chains); within 1e-13 relative of that
+// expression in long double for -100 .. 40 dB (tests/test_device_math_gpu.py::test_dipole_gain).
 AFS_HD inline double glottis_dipole_gain(double aspiration_db) {
   return 0.5e-7 * exp(aspiration_db * (2.302585092994045684 / 20.0));
 }

@@ -519,6 +519,20 @@ class Context:
         _native.check(st, self._h, "afs_tube_interpolate")
         return area, length
 
+    def device_math(self, op, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
+        """Diagnostics (tree solver): out[k] = op(a[k], b[k]) with the synthesis kernel's device-only
+        arithmetic (csrc/tree_core.h, compiled with the kernel's flags); op: a name or value of
+        _native.MATH_OPS (afs_device_math.h), b: as many operands as a (zeros when the op takes one)."""
+        op = _native.MATH_OPS[op] if isinstance(op, str) else int(op)
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        b = np.zeros_like(a) if b is None else np.ascontiguousarray(b, dtype=np.float64).ravel()
+        if b.shape != a.shape:
+            raise ValueError("a and b must have the same number of operands")
+        out = np.zeros_like(a)
+        st = self._lib.afs_device_math(self._h, op, _vp(_addr(a)), _vp(_addr(b)), a.shape[0], _vp(_addr(out)))
+        _native.check(st, self._h, "afs_device_math")
+        return out
+
     def kernel_times(self) -> dict:
         """(profile=True contexts) summed device time and count of the synthesis-kernel (K1),
         noise-source-plan (K5) and output-stage (K6) launches since the previous call (waits for

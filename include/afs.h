@@ -277,6 +277,8 @@ afs_status afs_noise_plan_hops(afs_ctx *ctx, const afs_frame *frames, int32_t ro
  * (tests/test_plan_hops.py).  AFS_PLAN_DENSE=1 in the environment makes every hop read its dense
  * records (the per-sample plan bit for bit). */
 afs_status afs_plan_hop_words(afs_ctx *ctx, const uint8_t *hops, const double *ratio, int32_t n, uint64_t *words);
+/* Diagnostics: afs_device_math, the synthesis kernel's device-only arithmetic one operation at a time, is
+ * declared in afs_device_math.h beside this header. */
 
 /* Stateful sessions: B independent Synthesizer instances living on the device. */
 afs_status afs_session_create(afs_ctx *ctx, int32_t batch, const uint32_t *seeds, afs_session **s);

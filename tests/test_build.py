@@ -91,6 +91,27 @@ def test_scan_matches_depfile(source):
     assert build.include_graph(path) == build.depfile_sources(depfile) - {path}
 
 
+def test_depfiles_name_the_repository_relative_to_its_root(tree, monkeypatch):
+    """A built tree that is copied elsewhere still knows what its objects were built from: the depfiles
+    name the repository's files relative to its root, whatever the compiler wrote."""
+    depfile = _object("tds_plan.hip") + ".d"
+    text = open(depfile).read()
+    assert build.ROOT not in text and os.path.join("areafunctionsynthesis_amd", "csrc", "tree_plan.h") in text
+    path = os.path.join(build.CSRC, "tds_plan.hip")
+    assert build.depfile_sources(depfile) - {path} == build.include_graph(path)
+    # the same depfile read from a copy of the tree at another place names the copy's files
+    here, there = build.ROOT, os.path.join(tree.root, "moved")
+    moved = {os.path.join(there, os.path.relpath(f, here)) for f in build.include_graph(path) | {path}}
+    monkeypatch.setattr(build, "ROOT", there)
+    assert build.depfile_sources(depfile) == moved
+    # a file outside the repository (a system header) keeps its absolute name and is not the repository's
+    with open(depfile, "a") as fh:
+        fh.write("x.o: /usr/include/stdio.h with\\ space.h\n")
+    build.relocatable_depfile(depfile)
+    assert "/usr/include/stdio.h" in open(depfile).read() and "with\\ space.h" in open(depfile).read()
+    assert build.depfile_sources(depfile) == moved | {os.path.join(there, "with space.h")}
+
+
 def test_nothing_newer_nothing_stale(tree):
     assert tree.rebuilt() == ([], [])
     assert all(build.stale_reason(build.compile_command(s, objdir=build.OBJ)) is None for s in build.SOURCES)

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_functions():
-    txt = open(os.path.join(ROOT, "include", "afs.h")).read()
+    """The functions of the C ABI: include/afs.h and the diagnostics' header beside it."""
+    txt = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("afs.h", "afs_device_math.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(afs_[a-z_0-9]+)\s*\(", txt)))
 
