@@ -4,6 +4,7 @@ Run in the build container (needs /root/reference for oracle/_ref):
     python tests/golden/make_golden.py          (all files)
     python tests/golden/make_golden.py int16    (int16.npz only)
     python tests/golden/make_golden.py target_seq (target_seq.npz only)
+    python tests/golden/make_golden.py generic  (generic_tubes.npz only)
 
 Every expected value comes from oracle/_ref/libafsref.so -- the reference's own
 TdsModel / Tube / TriangularGlottis / IirFilter sources compiled unmodified and driven
@@ -90,7 +91,32 @@ def write_fulcher(ref: RefLib) -> None:
         fh.write(ref.fulcher_table())
 
 
+def write_generic(o: Oracle, ref: RefLib) -> None:
+    """Tubes the area-function model cannot make (tests/generic_tubes.py golden_cases: unequal section
+    lengths, broken tongue runs, teeth anywhere): the frames, and the reference build's first 2048
+    samples and rand() call count of every utterance."""
+    from generic_tubes import GOLDEN_SAMPLES, golden_cases
+    cases = golden_cases(o)
+    outs = np.zeros((len(cases), GOLDEN_SAMPLES))
+    num_out, calls = [], []
+    for i, (label, fr, hop, seed, fs) in enumerate(cases):
+        c0 = int(ref.lib.afsref_rand_calls())
+        y = ref.utterance(fr, hop, seed, fs)[:GOLDEN_SAMPLES]
+        calls.append(int(ref.lib.afsref_rand_calls()) - c0)
+        outs[i, : y.size] = y
+        num_out.append(y.size)
+    frames = np.ascontiguousarray(np.stack([c[1] for c in cases]))
+    np.savez_compressed(os.path.join(HERE, "generic_tubes.npz"), names=np.array([c[0] for c in cases]),
+                        frames=frames.view(np.uint8).reshape(frames.shape + (FRAME_DTYPE.itemsize,)),
+                        hop=np.array([c[2] for c in cases]), seed=np.array([c[3] for c in cases]),
+                        fs=np.array([c[4] for c in cases]), out=outs, num_out=np.array(num_out),
+                        rand_calls=np.array(calls, dtype=np.int64))
+
+
 def main() -> None:
+    if sys.argv[1:] == ["generic"]:
+        write_generic(Oracle(), RefLib())
+        return
     if sys.argv[1:] == ["fulcher"]:
         write_fulcher(RefLib())
         return
@@ -172,6 +198,7 @@ def main() -> None:
     write_int16(r)
     write_fulcher(r)
     write_target_seq(o, r)
+    write_generic(o, r)
     print("golden vectors written to", HERE)
 
 

@@ -18,12 +18,11 @@ import numpy as np
 import pytest
 
 from areafunctionsynthesis_amd.frames import FRAME_DTYPE
+from plan_lib import HOP_DTYPE, PLAN_WORDS, PW_GAIN_G, _compare, _compare_hops
 
 pytestmark = pytest.mark.gpu
 
 EMU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-PW_GAIN_G = 15
-PLAN_WORDS = 16
 
 
 @pytest.fixture(scope="module")
@@ -60,23 +59,6 @@ def contexts():
     yield get
     for c in cache.values():
         c.close()
-
-
-def _compare(gpu, host, label):
-    assert gpu.shape == host.shape
-    exact = np.ones(PLAN_WORDS, dtype=bool)
-    exact[PW_GAIN_G] = False
-    diff = gpu[..., exact] != host[..., exact]
-    if diff.any():
-        r, t, w = np.argwhere(diff)[0]
-        words = np.flatnonzero(exact)
-        raise AssertionError(f"{label}: {int(diff.sum())} words differ; first: row {r} sample {t} word "
-                             f"{words[w]}: gpu {int(gpu[r, t, words[w]]):#x} host {int(host[r, t, words[w]]):#x}")
-    g = gpu[..., PW_GAIN_G].view(np.int64)
-    h = host[..., PW_GAIN_G].view(np.int64)
-    ulps = np.abs(g - h)  # (positive doubles: the bit patterns are ordered)
-    assert ulps.max() <= 1, (label, int(ulps.max()))
-    return int(np.count_nonzero(ulps))
 
 
 @pytest.mark.parametrize("two_mass", (False, True))
@@ -179,11 +161,6 @@ def test_k1_interpolation_equals_k5_geometry(oracle):
 # reference plan_hop_host (tests/emu/plan_emu.cpp emu_plan_hops), and the dense records of the
 # mixed hops' samples against plan_sample.
 # ---------------------------------------------------------------------------
-HOP_DTYPE = np.dtype([("p", "<u8", (PLAN_WORDS, 4)), ("kind", "u1", (PLAN_WORDS,)), ("mixed", "<u4"),
-                      ("dense", "<u4"), ("noise", "<u8")])
-assert HOP_DTYPE.itemsize == 544
-
-
 @pytest.fixture(scope="module")
 def host_hops():
     lib = ctypes.CDLL(os.path.join(EMU, "libplan_emu.so"))
@@ -200,35 +177,6 @@ def host_hops():
         assert lib.emu_plan_hops(frames.ctypes.data, rows, F, hop, s0, s1, fs, int(two_mass), out.ctypes.data) == 0
         return out
     return run
-
-
-def _compare_hops(ctx, host_hops, host_plans, frames, hop, s0, s1, fs, two_mass, label):
-    gh, gp = ctx.noise_plan_hops(frames, hop, s0, s1)
-    gh = gh.view(HOP_DTYPE)[..., 0]
-    hh = host_hops(frames, hop, s0, s1, fs, two_mass)
-    assert np.array_equal(gh["mixed"], hh["mixed"]), label
-    assert np.array_equal(gh["kind"], hh["kind"]), label
-    assert np.array_equal(gh["noise"], hh["noise"]), label  # (the dipoles and constrictions of every sample)
-    gw, hw = gh["p"].copy(), hh["p"].copy()
-    # the glottis gain (a constant word: p[15][0]) comes from the device pow: 1 ulp
-    ulps = np.abs(gw[..., 15, 0].view(np.int64) - hw[..., 15, 0].view(np.int64))
-    assert ulps.max() <= 1, (label, int(ulps.max()))
-    gw[..., 15, 0] = hw[..., 15, 0] = 0
-    diff = gw != hw
-    if diff.any():
-        r, q, w, j = np.argwhere(diff)[0]
-        raise AssertionError(f"{label}: {int(diff.sum())} inputs differ; first: row {r} slot {q} word {w} input {j}")
-    # the mixed hops' samples: their dense records
-    mixed_samples = np.zeros(gp.shape[:2], dtype=bool)
-    for r, q in np.argwhere(gh["mixed"] != 0):
-        h = s0 // hop + q
-        lo, hi = max(h * hop, s0), min((h + 1) * hop, s1)
-        mixed_samples[r, lo - s0:hi - s0] = True
-    if mixed_samples.any():
-        hp = host_plans(frames, hop, s0, s1, fs, two_mass)
-        _compare(gp[mixed_samples][None], hp[mixed_samples][None], label + " (mixed hops' dense records)")
-    assert not gp[~mixed_samples].any(), label  # nothing written for the other samples
-    return int(np.count_nonzero(gh["mixed"])), gh.size
 
 
 @pytest.mark.parametrize("two_mass", (False, True))
