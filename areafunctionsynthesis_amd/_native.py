@@ -53,6 +53,7 @@ EXPORTED = (
     "afs_session_latched",
     "afs_session_voice_state_bytes", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
     "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets", "afs_session_synthesize_ragged_packed",
+    "afs_session_synthesize_indexed", "afs_session_synthesize_indexed_packed",
     "afs_device_math",
 )
 
@@ -201,12 +202,17 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.afs_ragged_offsets.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
     lib.afs_session_synthesize_ragged_packed.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp,
                                                          vp, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_session_synthesize_indexed.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, vp, ctypes.c_int64,
+                                                   vp, vp, vp, ctypes.POINTER(AfsReport)]
+    lib.afs_session_synthesize_indexed_packed.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_int32,
+                                                          vp, vp, vp, vp, ctypes.POINTER(AfsReport)]
     lib.afs_device_math.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64, vp]
     lib.afs_device_math.restype = ctypes.c_int
     for name in ("afs_session_restart_voices", "afs_session_synthesize_ragged", "afs_session_synthesize_ragged_pcm",
                  "afs_session_latched", "afs_session_save_voices", "afs_session_load_voices", "afs_session_copy_voices",
                  "afs_synthesize_f32", "afs_synthesize_ragged_packed", "afs_ragged_offsets",
-                 "afs_session_synthesize_ragged_packed"):
+                 "afs_session_synthesize_ragged_packed", "afs_session_synthesize_indexed",
+                 "afs_session_synthesize_indexed_packed"):
         getattr(lib, name).restype = ctypes.c_int
     for name in ("afs_create", "afs_set_stream", "afs_synchronize", "afs_synthesize",
                  "afs_session_create", "afs_session_synthesize", "afs_session_reset", "afs_af_to_frames",

@@ -21,6 +21,7 @@
 #include "afs_audio.h"
 #include "afs_ctx.h"
 #include "afs_device_math.h"
+#include "afs_indexed.h"
 #include "afs_model.h"
 #include "afs_ragged_order.h"
 #include "afs_session_kernels.h"
@@ -1407,20 +1408,25 @@ static afs_status session_core(afs_session *s, const afs_frame *frames, int32_t 
 // The launch layout of a pool call and its per-voice arrays on the device, sent as ragged_layout sends
 // a ragged call's (the context's pinned buffer, one upload on the stream, the event that guards its
 // reuse): block_end, the slot order and stand-ins of afs::pool_order, the transitions each voice plays
-// (K5's and K6's row_hops), then the frame counts and latch flags that launch_pool_rows reads.
+// (K5's and K6's row_hops), then the frame counts and latch flags that launch_pool_rows reads; behind them
+// a packed call's row starts and an indexed call's frame start indices (launch_pool_rows_indexed).
 struct PoolArrays {
   const int32_t *count = nullptr, *latched = nullptr;
+  const int64_t *start = nullptr;
 };
 static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *num_frames, const int32_t *trans, int upb,
-                              int hop, SynthCall *call, PoolArrays *pa, const int64_t *row_base = nullptr) {
+                              int hop, SynthCall *call, PoolArrays *pa, const int64_t *row_base = nullptr,
+                              const int64_t *frame_start = nullptr) {
   const int B = s->B;
   const afs::RaggedOrder ro = afs::pool_order(trans, B, upb, hop);
   const size_t slots = ro.order.size();
   const size_t end_bytes = (size_t)ro.grid * sizeof(int64_t), slot_bytes = slots * sizeof(int32_t);
   const size_t row_bytes = (size_t)B * sizeof(int32_t);
-  // (a packed call's row starts ride behind the per-voice arrays, on an 8-byte boundary)
+  // (a packed call's row starts and an indexed call's frame starts ride behind the per-voice arrays, on
+  // an 8-byte boundary)
   const size_t base0 = (end_bytes + 2 * slot_bytes + 3 * row_bytes + 7) / 8 * 8;
-  const size_t bytes = base0 + (row_base ? (size_t)B * sizeof(int64_t) : 0);
+  const size_t start0 = base0 + (row_base ? (size_t)B * sizeof(int64_t) : 0);
+  const size_t bytes = start0 + (frame_start ? (size_t)B * sizeof(int64_t) : 0);
   if (!c->ev_ragged) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_ragged, hipEventDisableTiming));
   else HIP_TRY(c, hipEventSynchronize(c->ev_ragged));
   HIP_TRY(c, c->ragged_host.reserve(bytes));
@@ -1435,6 +1441,7 @@ static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *n
   int32_t *lat = (int32_t *)(h + rows0 + 2 * row_bytes);
   for (int u = 0; u < B; ++u) lat[u] = s->latch[(size_t)u] ? 1 : 0;
   if (row_base) std::memcpy(h + base0, row_base, (size_t)B * sizeof(int64_t));
+  if (frame_start) std::memcpy(h + start0, frame_start, (size_t)B * sizeof(int64_t));
   HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_ragged, c->stream));
   call->row_base = row_base ? (const int64_t *)(d + base0) : nullptr;
@@ -1445,6 +1452,7 @@ static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *n
   call->ragged.row_hops = (const int32_t *)(d + rows0);
   pa->count = (const int32_t *)(d + rows0 + row_bytes);
   pa->latched = (const int32_t *)(d + rows0 + 2 * row_bytes);
+  pa->start = frame_start ? (const int64_t *)(d + start0) : nullptr;
   return AFS_OK;
 }
 
@@ -1454,20 +1462,37 @@ static afs_status pool_layout(afs_ctx *c, const afs_session *s, const int32_t *n
 // trans[u] transitions -- its count, less one while it is unlatched -- ntrans the largest; K1's blocks
 // come from pool_order, so a voice without a transition is in no slot, K5 skips its row and K6 returns
 // at once: nothing of it is read or written.
+// afs_session_synthesize_indexed and _indexed_packed (index: the frame source is one flat array, voice u's
+// frames at index->start[u]; fstride is not looked at, a row holds the largest count): only the gather of
+// the rows differs (launch_pool_rows_indexed), everything behind it is the same call.
 static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *frames, int64_t fstride,
                             const int32_t *num_frames, int32_t hop, double *out, int64_t ostride, double *taps_out,
                             void *pcm, int64_t pstride, bool want_pcm, uint8_t *nonfinite, int32_t *produced,
                             afs_report *rep, int32_t format = AFS_SAMPLE_I16, bool packed = false,
-                            const int64_t *offsets = nullptr) {
+                            const int64_t *offsets = nullptr, const afs::FrameIndex *index = nullptr) {
   if (!s) return AFS_ERR_INVALID_ARGUMENT;
   afs_ctx *c = s->ctx;
   if (!tree(c)) return fail(c, AFS_ERR_UNSUPPORTED, "%s: tree solver only", fn);
-  if (hop < 1 || fstride < 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need hop>=1, frame_stride>=0", fn);
+  if (hop < 1) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need hop>=1", fn);
+  if (fstride < 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need frame_stride>=0", fn);
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   if (!num_frames || is_device_ptr(num_frames))
     return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: num_frames is a host array of batch counts", fn);
   if (taps_out && c->n_taps <= 0) return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: no taps set (afs_set_taps)", fn);
   const int B = s->B;
+  afs::IndexedSpans spans;
+  if (index) {
+    if (index->start && is_device_ptr(index->start))
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: frame_start is a host array of batch indices", fn);
+    const afs::IndexedCheck ic = afs::indexed_check(index->start, num_frames, B, index->total);
+    if (ic.fault == afs::INDEXED_TOTAL || ic.fault == afs::INDEXED_NULL)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: need total_frames >= 0 and a frame_start array", fn);
+    if (ic.fault != afs::INDEXED_OK)
+      return fail(c, AFS_ERR_INVALID_ARGUMENT, "%s: voice %d: frames %lld .. +%d outside 0..total_frames = %lld", fn,
+                  ic.voice, (long long)index->start[ic.voice], num_frames[ic.voice], (long long)index->total);
+    spans = afs::indexed_spans(index->start, num_frames, B);
+    fstride = spans.longest;  // (the frames a row holds besides the latch)
+  }
   std::vector<int32_t> trans((size_t)B);
   int32_t ntrans = 0;
   int64_t samples = 0;
@@ -1521,7 +1546,29 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   // through the context's staging buffer)
   Frames fr;
   const size_t fbytes = (size_t)B * (size_t)fstride * sizeof(afs_frame);
-  if (is_device_ptr(frames) && (reinterpret_cast<uintptr_t>(frames) & 15)) {
+  std::vector<int64_t> start;  // an indexed call: where the gather finds each voice's frames in fr.dev
+  if (index) {
+    start.resize((size_t)B);
+    if (!is_device_ptr(frames)) {
+      // a host corpus: the live spans alone, back to back through the session's pinned buffer, one upload
+      const size_t live_bytes = (size_t)spans.sum * sizeof(afs_frame);
+      HIP_TRY(c, s->hframes.reserve(live_bytes));
+      HIP_TRY(c, c->stage_in.reserve(live_bytes));
+      afs::indexed_compact(frames, index->start, num_frames, B, s->hframes.as<afs_frame>(), start.data());
+      HIP_TRY(c, hipMemcpyAsync(c->stage_in.data(), s->hframes.data(), live_bytes, hipMemcpyHostToDevice, c->stream));
+      fr.dev = c->stage_in.as<const afs_frame>();
+    } else if (reinterpret_cast<uintptr_t>(frames) & 15) {
+      // (device memory at another alignment: the hull of the live spans through the staging buffer)
+      const size_t hull_bytes = (size_t)(spans.end - spans.first) * sizeof(afs_frame);
+      HIP_TRY(c, c->stage_in.reserve(hull_bytes));
+      HIP_TRY(c, hipMemcpyAsync(c->stage_in.data(), frames + spans.first, hull_bytes, hipMemcpyDeviceToDevice, c->stream));
+      afs::indexed_rebase(index->start, num_frames, B, spans.first, start.data());
+      fr.dev = c->stage_in.as<const afs_frame>();
+    } else {  // read in place
+      afs::indexed_rebase(index->start, num_frames, B, 0, start.data());
+      fr.dev = frames;
+    }
+  } else if (is_device_ptr(frames) && (reinterpret_cast<uintptr_t>(frames) & 15)) {
     HIP_TRY(c, c->stage_in.reserve(fbytes));
     HIP_TRY(c, hipMemcpyAsync(c->stage_in.data(), frames, fbytes, hipMemcpyDeviceToDevice, c->stream));
     fr.dev = c->stage_in.as<const afs_frame>();
@@ -1532,7 +1579,8 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   PoolArrays pa;
   const int upb = s->lanes == afs::TREE_VOICE_W ? 1 : afs::TREE_UPB;
   call.so = plain_order(c);
-  if ((st = pool_layout(c, s, num_frames, trans.data(), upb, hop, &call, &pa, packed ? row_base.data() : nullptr)) != AFS_OK)
+  if ((st = pool_layout(c, s, num_frames, trans.data(), upb, hop, &call, &pa, packed ? row_base.data() : nullptr,
+                        index ? start.data() : nullptr)) != AFS_OK)
     return st;
   const size_t had = c->pool_rows.capacity();
   HIP_TRY(c, c->pool_rows.reserve((size_t)B * (size_t)(fstride + 1) * sizeof(afs_frame)));
@@ -1540,7 +1588,11 @@ static afs_status pool_core(afs_session *s, const char *fn, const afs_frame *fra
   // transition included, and never uses it)
   if (c->pool_rows.capacity() != had) HIP_TRY(c, hipMemsetAsync(c->pool_rows.data(), 0, c->pool_rows.capacity(), c->stream));
   afs_frame *rows = c->pool_rows.as<afs_frame>();
-  HIP_TRY(c, afs::launch_pool_rows(fr.dev, fstride, pa.count, pa.latched, B, rows, s->pair.as<afs_frame>(), c->stream));
+  if (index)
+    HIP_TRY(c, afs::launch_pool_rows_indexed(fr.dev, pa.start, fstride, pa.count, pa.latched, B, rows,
+                                             s->pair.as<afs_frame>(), c->stream));
+  else
+    HIP_TRY(c, afs::launch_pool_rows(fr.dev, fstride, pa.count, pa.latched, B, rows, s->pair.as<afs_frame>(), c->stream));
   if (ntrans == 0) {  // the voices that got frames only latch: no synthesis kernel runs
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     done(0);
@@ -1858,6 +1910,24 @@ afs_status afs_session_synthesize_ragged_packed(afs_session *s, const afs_frame 
                                                 afs_report *rep) {
   return pool_core(s, "afs_session_synthesize_ragged_packed", frames, frame_stride, num_frames, hop, nullptr, 0, nullptr,
                    out, 0, true, nonfinite, produced, rep, format, true, offsets);
+}
+
+afs_status afs_session_synthesize_indexed(afs_session *s, const afs_frame *frames, int64_t total_frames,
+                                          const int64_t *frame_start, const int32_t *num_frames, int32_t hop,
+                                          double *out, int64_t out_stride, double *taps_out, uint8_t *nonfinite,
+                                          int32_t *produced, afs_report *rep) {
+  const afs::FrameIndex index{frame_start, total_frames};
+  return pool_core(s, "afs_session_synthesize_indexed", frames, 0, num_frames, hop, out, out_stride, taps_out, nullptr, 0,
+                   false, nonfinite, produced, rep, AFS_SAMPLE_I16, false, nullptr, &index);
+}
+
+afs_status afs_session_synthesize_indexed_packed(afs_session *s, const afs_frame *frames, int64_t total_frames,
+                                                 const int64_t *frame_start, const int32_t *num_frames, int32_t hop,
+                                                 int32_t format, void *out, const int64_t *offsets, uint8_t *nonfinite,
+                                                 int32_t *produced, afs_report *rep) {
+  const afs::FrameIndex index{frame_start, total_frames};
+  return pool_core(s, "afs_session_synthesize_indexed_packed", frames, 0, num_frames, hop, nullptr, 0, nullptr, out, 0,
+                   true, nonfinite, produced, rep, format, true, offsets, &index);
 }
 
 afs_status afs_af_to_frames(afs_ctx *c, const double *params, int64_t n, afs_frame *frames) {

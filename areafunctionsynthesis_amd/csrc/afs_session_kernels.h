@@ -28,6 +28,12 @@ hipError_t launch_voice_reset(void *lane_state, double *lds_state, const int32_t
 // frames, rows and pair are 16-byte aligned.
 hipError_t launch_pool_rows(const afs_frame *frames, int64_t frame_stride, const int32_t *count,
                             const int32_t *latched, int B, afs_frame *rows, afs_frame *pair, hipStream_t st);
+// The indexed form (afs_session_synthesize_indexed): the same rows and latches, voice u's frames being
+// frames[start[u] + k] of one flat array, start a device array of B indices, and a row holding
+// longest + 1 frames (longest: the largest count).  Spans may overlap: frames is only read.  The start of
+// a voice with count[u] == 0 is not loaded.  The same kernel body, one wave per frame of a row.
+hipError_t launch_pool_rows_indexed(const afs_frame *frames, const int64_t *start, int64_t longest, const int32_t *count,
+                                    const int32_t *latched, int B, afs_frame *rows, afs_frame *pair, hipStream_t st);
 
 // Voice records (afs_voice_state.h; afs_session_save_voices, _load_voices, _copy_voices).  The session's
 // three buffers that hold a voice: the lane registers, the saved LDS images, the frame pairs.

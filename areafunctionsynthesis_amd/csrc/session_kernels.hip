@@ -36,24 +36,39 @@ constexpr int FRAME_VECS = (int)(sizeof(afs_frame) / 16);  // 67
 static_assert(sizeof(afs_frame) % 16 == 0 && FRAME_VECS <= 128, "a frame is at most two 16-byte vectors per lane");
 constexpr int ROWS_WAVES = 4;  // waves per block: frames j = blockIdx.y * 4 + wave of voice blockIdx.x
 
+// Where voice u's frames begin in the caller's array, in frames, and the frames a row holds besides the
+// latch: the rectangle of afs_session_synthesize_ragged (u * frame_stride) or the start indices of
+// afs_session_synthesize_indexed (start[u], a device array; the rows hold row_frames, the largest count).
+struct RectFrames {
+  int64_t frame_stride;
+  __device__ int64_t base(int u) const { return (int64_t)u * frame_stride; }
+  __device__ int64_t row_frames() const { return frame_stride; }
+};
+struct IndexedFrames {
+  const int64_t *start;
+  int64_t longest;
+  __device__ int64_t base(int u) const { return start[u]; }
+  __device__ int64_t row_frames() const { return longest; }
+};
+
 // Wave (u, j) builds frame j of voice u's row; lane l moves vectors l and l + 64.  Wave (u, 0) alone
 // touches pair[u][0]: it loads the old latch (a latched voice's row frame 0) and the new one, the last
 // frame supplied, and only then stores either.
-__global__ void __launch_bounds__(64 * ROWS_WAVES) pool_rows_kernel(const uint4 *frames, int64_t frame_stride,
-                                                                     const int32_t *count, const int32_t *latched, int B,
-                                                                     uint4 *rows, uint4 *pair) {
+template <class Source>
+__device__ __forceinline__ void pool_rows_body(const uint4 *frames, const Source &at, const int32_t *count,
+                                               const int32_t *latched, int B, uint4 *rows, uint4 *pair) {
   const int u = blockIdx.x;
   const int lane = (int)threadIdx.x & 63;
   const int j = (int)blockIdx.y * ROWS_WAVES + (int)threadIdx.x / 64;
   if (u >= B) return;
   const int c = count[u];
-  if (c <= 0) return;  // (idle: nothing of this voice is read or written)
+  if (c <= 0) return;  // (idle: nothing of this voice is read or written, its start index included)
   const int lat = latched[u] != 0 ? 1 : 0;
-  if (j >= c + lat) return;  // (wave-uniform; c + lat <= frame_stride + 1)
-  const uint4 *src_u = frames + (int64_t)u * frame_stride * FRAME_VECS;
+  if (j >= c + lat) return;  // (wave-uniform; c + lat <= row_frames + 1)
+  const uint4 *src_u = frames + at.base(u) * FRAME_VECS;
   uint4 *latch = pair + (int64_t)u * 2 * FRAME_VECS;
   const uint4 *src = (j == 0 && lat) ? latch : src_u + (int64_t)(j - lat) * FRAME_VECS;
-  uint4 *dst = rows + ((int64_t)u * (frame_stride + 1) + j) * FRAME_VECS;
+  uint4 *dst = rows + ((int64_t)u * (at.row_frames() + 1) + j) * FRAME_VECS;
   const bool two = lane + 64 < FRAME_VECS;
   const uint4 a0 = src[lane];
   uint4 a1 = a0;
@@ -68,6 +83,20 @@ __global__ void __launch_bounds__(64 * ROWS_WAVES) pool_rows_kernel(const uint4 
   }
   dst[lane] = a0;
   if (two) dst[lane + 64] = a1;
+}
+
+__global__ void __launch_bounds__(64 * ROWS_WAVES) pool_rows_kernel(const uint4 *frames, int64_t frame_stride,
+                                                                     const int32_t *count, const int32_t *latched, int B,
+                                                                     uint4 *rows, uint4 *pair) {
+  pool_rows_body(frames, RectFrames{frame_stride}, count, latched, B, rows, pair);
+}
+
+// the same rows from a flat array: voice u's frames are frames[start[u] .. start[u] + count[u])
+__global__ void __launch_bounds__(64 * ROWS_WAVES) pool_rows_indexed_kernel(const uint4 *frames, const int64_t *start,
+                                                                             int64_t longest, const int32_t *count,
+                                                                             const int32_t *latched, int B, uint4 *rows,
+                                                                             uint4 *pair) {
+  pool_rows_body(frames, IndexedFrames{start, longest}, count, latched, B, rows, pair);
 }
 
 // ---- voice records: session buffers <-> packed records (afs_voice_state.h) ----
@@ -135,6 +164,17 @@ hipError_t launch_pool_rows(const afs_frame *frames, int64_t frame_stride, const
   return hipGetLastError();
 }
 
+hipError_t launch_pool_rows_indexed(const afs_frame *frames, const int64_t *start, int64_t longest, const int32_t *count,
+                                    const int32_t *latched, int B, afs_frame *rows, afs_frame *pair, hipStream_t st) {
+  if (B <= 0 || longest <= 0) return hipSuccess;
+  if ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(pair)) & 15)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)B, (unsigned)((longest + 1 + ROWS_WAVES - 1) / ROWS_WAVES)), block(64 * ROWS_WAVES);
+  hipLaunchKernelGGL(pool_rows_indexed_kernel, grid, block, 0, st, (const uint4 *)frames, start, longest, count, latched,
+                     B, (uint4 *)rows, (uint4 *)pair);
+  return hipGetLastError();
+}
+
 VoiceStateLayout voice_state_layout_for(int lanes) {
   return voice_state_layout(lanes, lanes == 64 ? (int64_t)sizeof(Lane<64>) : (int64_t)sizeof(Lane<TREE_W>), X_TOTAL,
                             (int64_t)sizeof(afs_frame));
@@ -172,6 +212,7 @@ hipError_t preload_session_kernels() {
   for (const void *k : {reinterpret_cast<const void *>(voice_reset_kernel<TREE_W>),
                         reinterpret_cast<const void *>(voice_reset_kernel<64>),
                         reinterpret_cast<const void *>(pool_rows_kernel),
+                        reinterpret_cast<const void *>(pool_rows_indexed_kernel),
                         reinterpret_cast<const void *>(voice_gather_kernel),
                         reinterpret_cast<const void *>(voice_scatter_kernel)}) {
     const hipError_t x = hipFuncGetAttributes(&at, k);

@@ -12,6 +12,8 @@
 * :meth:`Context.synthesize_stream` -- continuous batching: a corpus streamed through a pool of
   voices (:meth:`Synthesizer.synthesize_frames`, :meth:`Synthesizer.restart`), a few frames per
   voice and call.
+* :meth:`Context.synthesize_corpus` -- the same over one flat corpus array that the voices read in
+  place by index (:func:`stream_corpus`): no frame and no audio array is built per step.
 * :meth:`Context.synthesize_candidates` -- branching: a prefix played once, forked into K voices
   (:meth:`Synthesizer.fork`, :meth:`Synthesizer.save_voices`, :meth:`Synthesizer.load_voices`,
   :meth:`Synthesizer.copy_voices`), each playing its own continuation.
@@ -439,6 +441,34 @@ class Context:
                                          finished=finished)
         finally:
             session.close()
+
+    def synthesize_corpus(self, frames, frame_offsets, hop: int, slots: int, chunk_frames: int, seeds=None,
+                          pcm: bool = True, f32: bool = False, out=None):
+        """Continuous batching over a flat corpus (tree solver): ``frames`` is one 1-D FRAME_DTYPE array or
+        GPU tensor holding every utterance, utterance i at ``frames[frame_offsets[i]:frame_offsets[i + 1]]``
+        (at least 2 frames).  A session of ``slots`` voices plays up to ``chunk_frames`` frames of every
+        live utterance per step, reading them in place by index (afs_session_synthesize_indexed_packed) and
+        writing each sample at its final offset; a voice that finishes takes the next utterance
+        (:func:`stream_corpus`).  Returns ``(flat, offsets, nonfinite)``: utterance i's audio is
+        ``flat[offsets[i]:offsets[i + 1]]``, int16 (``pcm``) or float32 (``f32``), bit for bit
+        ``synthesize_ragged(..., packed=True)`` of the corpus and ``synthesize(utterance_i[None], hop,
+        seeds=[seed_i])`` on a context of the session's lane width.  ``seeds``: one per utterance (None:
+        index + 1).  ``out``: a 1-D buffer of ``offsets[n]`` samples of the caller's, numpy or GPU tensor."""
+        _, dtype = _sample_format(pcm, f32, True)
+        buf = out
+        if buf is None:  # (the audio stays on this context's device for the whole run and comes back once)
+            import torch
+            counts = np.diff(np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1))
+            total = int((np.maximum(counts, 1) - 1).sum()) * int(hop)
+            buf = torch.zeros(total, dtype=torch.int16 if dtype == np.int16 else torch.float32,
+                              device=torch.device("cuda", self.device))
+        session = Synthesizer(self, int(slots))
+        try:
+            flat, offsets, nonfinite = stream_corpus(session, frames, frame_offsets, hop, chunk_frames, seeds=seeds,
+                                                     pcm=pcm, f32=f32, out=buf)
+        finally:
+            session.close()
+        return (flat.cpu().numpy() if out is None else flat), offsets, nonfinite
 
     def synthesize_candidates(self, prefix, candidates, hop: int, seed: int = 1, pcm: bool = False):
         """Branching (tree solver): ``prefix[Fp]`` is played once, on voice 0 of a session of K voices
@@ -868,7 +898,7 @@ class Synthesizer:
 
     def synthesize_frames(self, frames, num_frames, hop: int, out=None, taps: bool = False, taps_out=None,
                           pcm: bool = False, report: bool = False, f32: bool = False, packed: bool = False,
-                          offsets=None):
+                          offsets=None, frame_start=None):
         """afs_session_synthesize_ragged: every voice plays its own number of frames in one call.
         ``frames``: a ``[batch, Fmax]`` FRAME_DTYPE array or uint8 GPU tensor ``[batch, Fmax, 1072]`` of
         which voice u plays the first ``num_frames[u]`` (the rest is never read), or a list of per-voice
@@ -884,7 +914,11 @@ class Synthesizer:
         ``(flat, offsets, produced)`` (then the report) -- voice u's samples at ``flat[offsets[u]:offsets[u]
         + produced[u]]`` of a 1-D int16 or float32 array, tightly in voice order (``offsets`` int64
         ``[batch + 1]``), or at the caller's ``offsets[batch]`` (an idle voice's is not looked at); ``out``:
-        a 1-D numpy array or GPU tensor to receive them.  ``f32`` needs ``packed``."""
+        a 1-D numpy array or GPU tensor to receive them.  ``f32`` needs ``packed``.
+        ``frame_start``: int64 ``[batch]`` (afs_session_synthesize_indexed, _indexed_packed): ``frames`` is
+        then one flat 1-D FRAME_DTYPE array, or a GPU tensor of whole frames, and voice u plays
+        ``frames[frame_start[u]:frame_start[u] + num_frames[u]]`` -- read in place on the device; spans may
+        overlap, an idle voice's start is not looked at.  Float64 (with taps) or packed int16 / float32."""
         fmt, dtype = _sample_format(pcm, f32, packed)
         if f32 and not packed:
             raise ValueError("a float32 pool call is packed: pass packed=True")
@@ -894,6 +928,9 @@ class Synthesizer:
         if pcm and taps:
             raise ValueError("the PCM calls have no taps")
         B = self.batch
+        if frame_start is not None:
+            return self._synthesize_indexed(frames, frame_start, num_frames, int(hop), out, taps, taps_out, fmt, dtype,
+                                            packed, offsets, report)
         if isinstance(frames, (list, tuple)):
             rows = [np.ascontiguousarray(f, dtype=FRAME_DTYPE).reshape(-1) for f in frames]
             if num_frames is None:
@@ -968,6 +1005,84 @@ class Synthesizer:
                                                          _vp(_addr(produced)), ctypes.byref(rep) if report else None)
             _native.check(st, self.ctx.handle, "afs_session_synthesize_ragged")
         res = (out, produced) + ((taps_out,) if taps else ())
+        if report:
+            res += ({"device_ms": rep.device_ms, "samples": rep.samples,
+                     "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
+                     "nonfinite": nonfinite},)
+        return res
+
+    def _synthesize_indexed(self, frames, frame_start, num_frames, hop, out, taps, taps_out, fmt, dtype, packed, offsets,
+                            report):
+        """:meth:`synthesize_frames` with ``frame_start``: the indexed calls.  Numpy over the voices
+        throughout -- a step of a large pool costs no Python loop."""
+        B = self.batch
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != FRAME_DTYPE or frames.ndim != 1 or not frames.flags["C_CONTIGUOUS"]:
+                raise ValueError("indexed frames must be a contiguous 1-D FRAME_DTYPE array")
+            total = int(frames.shape[0])
+        else:
+            total, rest = divmod(_nbytes(frames), FRAME_DTYPE.itemsize)
+            if rest or (hasattr(frames, "is_contiguous") and not frames.is_contiguous()):
+                raise ValueError("device frames must be contiguous and hold whole frames of 1072 bytes")
+        if num_frames is None:
+            raise ValueError("num_frames must hold batch counts")
+        counts = np.ascontiguousarray(num_frames, dtype=np.int32)
+        starts = np.ascontiguousarray(frame_start, dtype=np.int64)
+        if counts.shape != (B,) or starts.shape != (B,):
+            raise ValueError("num_frames and frame_start must hold batch entries")
+        produced = np.zeros(B, dtype=np.int32)
+        nonfinite = np.zeros(B, dtype=np.uint8) if report else None
+        rep = _native.AfsReport()
+        lengths = np.where(counts > 0, counts.astype(np.int64) - 1 + self.latched, 0) * hop
+        if fmt is not None:
+            if not packed:
+                raise ValueError("an indexed int16 or float32 call is packed: pass packed=True")
+            own = None
+            if offsets is None:
+                off = np.zeros(B + 1, dtype=np.int64)
+                np.cumsum(np.maximum(lengths, 0), out=off[1:])
+                span = int(off[B])
+            else:
+                off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+                if off.size not in (B, B + 1):
+                    raise ValueError("offsets must hold one row start per utterance")
+                own = np.ascontiguousarray(off[:B])
+                span = int(np.where(lengths > 0, own + lengths, 0).max(initial=0))
+            if out is None:
+                out = np.zeros(span, dtype=dtype)
+            if len(out.shape) != 1:
+                raise ValueError("a packed out is 1-D")
+            if isinstance(out, np.ndarray):
+                if out.dtype != dtype or not out.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"a packed out must be contiguous {np.dtype(dtype).name}")
+            elif np.dtype(dtype).name not in str(out.dtype) or (out.shape[0] > 1 and int(out.stride(0)) != 1):
+                raise ValueError(f"a packed out must be contiguous {np.dtype(dtype).name}")
+            if int(out.shape[0]) < span:
+                raise ValueError(f"a packed out must hold {span} samples")
+            st = self._lib.afs_session_synthesize_indexed_packed(
+                self._h, _vp(_addr(frames)), total, _vp(_addr(starts)), _vp(_addr(counts)), hop, fmt,
+                _vp(_addr(out) if int(out.shape[0]) else 0), _vp(_addr(own)), _vp(_addr(nonfinite)), _vp(_addr(produced)),
+                ctypes.byref(rep) if report else None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_indexed_packed")
+            res = (out, off, produced)
+        else:
+            if out is None:
+                out = np.zeros((B, max(int(lengths.max(initial=0)), 0)), dtype=np.float64)
+            if len(out.shape) != 2 or int(out.shape[0]) != B or _nbytes(out) != B * int(out.shape[1]) * 8:
+                raise ValueError("out must be [batch, out_stride] doubles")
+            ostride = int(out.shape[1])
+            if taps:
+                nt = getattr(self.ctx, "n_taps", 0)
+                if taps_out is None:
+                    taps_out = np.zeros((B, nt, ostride), dtype=np.float64)
+                if nt and _nbytes(taps_out) != B * nt * ostride * 8:
+                    raise ValueError("taps_out must hold batch*n_taps*out_stride doubles")
+            st = self._lib.afs_session_synthesize_indexed(
+                self._h, _vp(_addr(frames)), total, _vp(_addr(starts)), _vp(_addr(counts)), hop,
+                _vp(_addr(out) if ostride else 0), ostride, _vp(_addr(taps_out) if taps else 0), _vp(_addr(nonfinite)),
+                _vp(_addr(produced)), ctypes.byref(rep) if report else None)
+            _native.check(st, self.ctx.handle, "afs_session_synthesize_indexed")
+            res = (out, produced) + ((taps_out,) if taps else ())
         if report:
             res += ({"device_ms": rep.device_ms, "samples": rep.samples,
                      "nonfinite_utterances": rep.nonfinite_utterances, "kernel": rep.kernel,
@@ -1111,6 +1226,75 @@ def stream_utterances(session, utterances, hop: int, chunk_frames: int, seeds=No
                 done = (index[u], audio[u])
                 index[u], frames[u], audio[u] = -1, None, None
                 yield done
+
+
+def stream_corpus(session, frames, frame_offsets, hop: int, chunk_frames: int, seeds=None, pcm: bool = True,
+                  f32: bool = False, out=None):
+    """The scheduler behind :meth:`Context.synthesize_corpus`: a flat corpus streamed through the voices
+    of a session with no frame moved on the host.  Written against ``batch``, ``restart(voices, seeds)``
+    and ``synthesize_frames(frames, num_frames, hop, out=, pcm=, f32=, packed=True, offsets=,
+    frame_start=, report=True) -> (out, offsets, produced, report)``.
+
+    ``frames``: the corpus, one flat FRAME_DTYPE array or GPU tensor; utterance i is
+    ``frames[frame_offsets[i]:frame_offsets[i + 1]]`` (``frame_offsets`` int64 ``[n + 1]``, at least 2
+    frames each).  Voices take the utterances in order.  Every step gives each live voice up to
+    ``chunk_frames`` of its remaining frames by index, and its audio goes to ``offsets[i]`` plus the samples
+    it has played: the output stage writes every sample at its final place.  A voice whose utterance has
+    ended is restarted with the next utterance's seed (``seeds[i]``; None: i + 1) before the next step.
+    The bookkeeping of a step is numpy over the voices.  Returns ``(flat, offsets, nonfinite)``:
+    ``offsets`` is :func:`ragged_offsets` of the corpus, utterance i's audio ``flat[offsets[i]:offsets[i +
+    1]]`` -- int16 (``pcm``) or float32 (``f32``) -- and ``nonfinite`` uint8 ``[n]``.  ``out``: the caller's own
+    1-D buffer of ``offsets[n]`` samples, numpy or a GPU tensor, returned as ``flat``; None: a numpy array
+    made here (a host buffer is staged whole on every step: :meth:`Context.synthesize_corpus` passes a
+    device buffer that lives for the whole run and copies it back once)."""
+    fmt, dtype = _sample_format(pcm, f32, True)
+    B, hop, chunk = int(session.batch), int(hop), int(chunk_frames)
+    if chunk < 1 or hop < 1:
+        raise ValueError("chunk_frames and hop must be at least 1")
+    fo = np.ascontiguousarray(frame_offsets, dtype=np.int64).reshape(-1)
+    if fo.size < 1 or fo[0] < 0:
+        raise ValueError("frame_offsets must hold n + 1 non-negative frame indices")
+    n = fo.size - 1
+    lens = np.diff(fo)
+    if n and int(lens.min()) < 2:
+        i = int(np.argmin(lens))
+        raise ValueError(f"utterance {i} has {int(lens[i])} frames: at least 2 (one transition)")
+    seed_of = np.arange(1, n + 1, dtype=np.uint32) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
+    if seed_of.shape != (n,):
+        raise ValueError("one seed per utterance")
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum((lens - 1) * hop, out=offsets[1:])
+    total = int(offsets[n])
+    flat = np.zeros(total, dtype=dtype) if out is None else out
+    nonfinite = np.zeros(n, dtype=np.uint8)
+    index = np.full(B, -1, dtype=np.int64)  # the utterance a voice plays, -1: none
+    pos = np.zeros(B, dtype=np.int64)       # the frames of it the voice has been given
+    played = np.zeros(B, dtype=np.int64)    # the samples of it the voice has produced
+    handed = 0
+    while True:
+        free = np.flatnonzero(index < 0)[:n - handed]
+        if free.size:
+            ids = np.arange(handed, handed + free.size)
+            index[free], pos[free], played[free] = ids, 0, 0
+            session.restart(free.astype(np.int32), seed_of[ids])
+            handed += int(free.size)
+        live = index >= 0
+        if not live.any():
+            break
+        i = np.where(live, index, 0)
+        counts = np.where(live, np.minimum(lens[i] - pos, chunk), 0).astype(np.int32)
+        starts = np.where(live, fo[i] + pos, 0)
+        dest = np.where(live, offsets[i] + played, 0)
+        res = session.synthesize_frames(frames, counts, hop, out=flat, pcm=pcm, f32=f32, packed=True, offsets=dest,
+                                        frame_start=starts, report=True)
+        played += res[2]
+        pos += counts
+        ended = live & (pos == lens[i])
+        if (played[ended] != (lens[i[ended]] - 1) * hop).any():
+            raise RuntimeError("an utterance ended with other than (F-1)*hop samples produced")
+        nonfinite[index[ended]] = res[-1]["nonfinite"][ended]
+        index[ended] = -1
+    return flat, offsets, nonfinite
 
 
 def branch_candidates(session, prefix, candidates, hop: int, pcm: bool = False):

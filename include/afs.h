@@ -499,6 +499,49 @@ afs_status afs_session_synthesize_ragged_packed(afs_session *s, const afs_frame 
                                                 const int32_t *num_frames, int32_t hop, int32_t format, void *out,
                                                 const int64_t *offsets, uint8_t *nonfinite, int32_t *produced,
                                                 afs_report *report);
+/* ---- Indexed voice pools: frames read in place from a flat corpus ---------------------------
+ * The voice pool's calls with the frames taken from one flat array instead of a rectangle: the packed
+ * sequence form the audio already has (afs_session_synthesize_ragged_packed), on the input side.  A
+ * corpus lies once in memory, frames[total_frames], and a step costs the host three integers per voice:
+ * where its next frames start, how many it plays, where its audio goes.  No frame moves on the host.
+ *
+ * afs_session_synthesize_indexed: afs_session_synthesize_ragged with voice u playing
+ * frames[frame_start[u] .. frame_start[u] + num_frames[u]).  frame_start and num_frames are HOST arrays
+ * of batch entries; frames is host or device memory.  Everything else is the ragged pool call's, word
+ * for word: the latch rule and the idle voice (c == 0: nothing of the voice is read or written, and its
+ * frame_start is not looked at), produced, nonfinite, report, taps_out, out_stride, and the alternation
+ * with every other session call on the same session.  A voice fed its utterance in pieces by these calls
+ * produces, bit for bit, the row, tap rows, rand() count and non-finite flag of afs_synthesize on that
+ * utterance alone with its seed (same lane width).  The spans of different voices may overlap or
+ * coincide (candidates that share a stretch, one utterance under two seeds): frames is only read, and no
+ * frame outside a live voice's span is ever read.
+ * afs_session_synthesize_indexed_packed: afs_session_synthesize_ragged_packed likewise -- format, out,
+ * offsets and their rules are that call's.
+ *
+ * Device frames aligned to 16 bytes are read in place by the gather of the call's frame rows: nothing of
+ * size total_frames is allocated or copied.  A device array at another alignment takes the ragged pool
+ * call's fallback, a copy to the staging buffer, restricted to the hull of the live spans (from the
+ * lowest frame_start to the highest end of a live voice).  Of a host array the library copies the live
+ * spans alone, back to back in voice order, into the session's pinned buffer, uploads that once and
+ * hands the gather the staging's own start indices: the bytes staged follow the sum of the counts, not
+ * total_frames (a span that two voices share is staged once for each).
+ *
+ * Every check is made on the host before anything is queued, and a refused call writes nothing.
+ * AFS_ERR_INVALID_ARGUMENT: total_frames < 0, a NULL frame_start or num_frames, a count below 0, a live
+ * voice with frame_start[u] < 0 or frame_start[u] + num_frames[u] > total_frames (compared without
+ * forming a sum that could overflow), frame_start in device memory, and everything the ragged pool calls
+ * refuse.  Tree solver only (AFS_ERR_UNSUPPORTED otherwise).
+ * Not covered: packed frame input for the one-shot afs_synthesize_ragged (the synthesis and plan kernels
+ * address frames by row x stride), frame_start in device memory, a hop per voice, afs_multi_synthesize,
+ * afs_synthesizer.hpp, the one-lane solvers, asynchronous session calls. */
+afs_status afs_session_synthesize_indexed(afs_session *s, const afs_frame *frames, int64_t total_frames,
+                                          const int64_t *frame_start, const int32_t *num_frames, int32_t hop,
+                                          double *out, int64_t out_stride, double *taps_out, uint8_t *nonfinite,
+                                          int32_t *produced, afs_report *report);
+afs_status afs_session_synthesize_indexed_packed(afs_session *s, const afs_frame *frames, int64_t total_frames,
+                                                 const int64_t *frame_start, const int32_t *num_frames, int32_t hop,
+                                                 int32_t format, void *out, const int64_t *offsets,
+                                                 uint8_t *nonfinite, int32_t *produced, afs_report *report);
 /* Diagnostics: the device memory the context holds now (its buffers grow on demand and are kept).
  * total_bytes: all of it; sample_buffer_bytes: the part that holds one fp64 value per
  * utterance-sample -- the flow and section-25 windows of a launch, a staged fp64 out or taps of a host
@@ -508,7 +551,11 @@ afs_status afs_session_synthesize_ragged_packed(afs_session *s, const afs_frame 
  * staging of voice records (afs_session_copy_voices, host records of _save_voices / _load_voices: n
  * records, grown on demand and kept); neither is a sample buffer.  It also counts what a packed or
  * float32 call adds: the row starts on the device (8 B per utterance, beside the ragged layout) and the
- * staging of a host destination (its span in samples of its format, in the int16 staging's buffer). */
+ * staging of a host destination (its span in samples of its format, in the int16 staging's buffer).  An
+ * indexed pool call (afs_session_synthesize_indexed) adds the frame start indices on the device (8 B per
+ * voice, beside the same layout) and nothing that grows with total_frames: its frame rows are batch x
+ * (the largest count + 1) frames, and only a host or misaligned corpus is staged (the live spans, or
+ * their hull, in the frames' staging buffer). */
 typedef struct afs_memory_info {
   int64_t total_bytes;
   int64_t sample_buffer_bytes;
